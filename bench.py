@@ -10,6 +10,11 @@ collective; the only collectives are the timing barrier and max).
 value = user data processed by the step (k*shard_bytes per stripe for the
 encode plus the same for the reconstruct) / step time, GiB/s, all ranks.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps and prints the line. --full adds what
+takes runs of its own after the timed region: the output check against the oracle
+(`verified`), the CPU baseline (`cpu_baseline`) and the configs[4] GPU leg (`c4_gpu`).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -27,9 +32,11 @@ import reedsol_amd as R  # noqa: E402  (after torch: one HIP runtime)
 from reedsol_amd.sharding import all_ok, max_over_ranks  # noqa: E402
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BUDGET_BYTES = 32 << 20  # --dump-outputs: all files together, as float32
+DUMP_SEED = 0xD0C5
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -39,12 +46,21 @@ def parse():
     ap.add_argument("--shard-bytes", type=int, default=1 << 20)
     ap.add_argument("--stripes", type=int, default=4096, help="stripes per GPU")
     ap.add_argument("--erase", type=str, default="0,1,2,3", help="erased original indices")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget for the CPU baseline leg (0 = skip)")
-    ap.add_argument("--no-verify", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also verify the outputs against the oracle and run the CPU "
+                         "baseline and the configs[4] GPU leg (the options below shape those legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (parity, restored) as DIR/<name>.npy, float32; "
+                         "a fixed seeded sample where an output is larger than its share of "
+                         f"{DUMP_BUDGET_BYTES >> 20} MiB")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0,
+                    help="--full: budget for the CPU baseline leg (0 = skip)")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the output check")
     ap.add_argument("--c4-reps", type=int, default=5,
-                    help="BASELINE configs[4] (RS(200,55) 256 KiB x 512) GPU leg after the timed region, N=1 (0 = skip)")
+                    help="--full: BASELINE configs[4] (RS(200,55) 256 KiB x 512) GPU leg after the timed region, "
+                         "N=1 (0 = skip)")
     ap.add_argument("--c4-stripes", type=int, default=512, help="stripes of the configs[4] leg (SURVEY.md §8(d): 512)")
-    return ap.parse_args()
+    return ap.parse_args(argv)
 
 
 def _threads():
@@ -253,8 +269,28 @@ def load_traffic(kernel_names):
     return {n: t[n] for n in kernel_names if n in t}
 
 
-def main():
-    args = parse()
+def dump_sample(numel, count, which):
+    """Flat positions of the dumped sample of output number `which`: `count` draws from
+    DUMP_SEED, sorted (the same positions for the same shape in every run and build)."""
+    rng = np.random.default_rng([DUMP_SEED, which])
+    return np.sort(rng.integers(0, numel, count, dtype=np.int64))
+
+
+def dump_outputs(path, outputs):
+    """Write each output tensor of the timed path as path/<name>.npy (float32): whole in
+    its own shape, or, where it is larger than its share of DUMP_BUDGET_BYTES, the 1-D
+    sample of dump_sample()."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // 4 // len(outputs)  # elements per file
+    for i, (name, t) in enumerate(outputs.items()):
+        if t.numel() > share:
+            idx = torch.from_numpy(dump_sample(t.numel(), share, i)).to(t.device)
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(np.float32))
+
+
+def main(argv=None):
+    args = parse(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -315,8 +351,11 @@ def main():
     enc_ms = max_over_ranks(enc_ms, device=dev)
     rec_ms = max_over_ranks(rec_ms, device=dev)
 
+    if args.dump_outputs and rank == 0:  # rank 0's batch: the outputs of its last timed step
+        dump_outputs(args.dump_outputs, {"parity": parity, "restored": restored})
+
     ok = None
-    if not args.no_verify:  # restored == erased data, and 2 whole stripes' parity == the oracle's
+    if args.full and not args.no_verify:  # restored == erased data, and 2 whole stripes' parity == the oracle's
         ok = all_ok(bool(torch.equal(restored, data[:, erase])) and verify_parity(k, m, data, parity), device=dev)
 
     if rank == 0:
@@ -346,10 +385,10 @@ def main():
                                         "launched": sorted(launched[kk])}
                                    for kk, v in kinds.items()}}
         cpu = None  # host-core baseline: rank 0 at N=1 only (the driver's N>1 runs skip it)
-        if args.cpu_seconds > 0 and world == 1:
+        if args.full and args.cpu_seconds > 0 and world == 1:
             cpu = cpu_baseline(k, m, sb, erase, args.cpu_seconds)
         c4 = None  # configs[4] on the GPU (not part of `value`)
-        if args.c4_reps > 0 and world == 1:
+        if args.full and args.c4_reps > 0 and world == 1:
             del data, parity, restored
             torch.cuda.empty_cache()
             try:
@@ -366,6 +405,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(t / args.steps * 1e3, 3),
             "higher_is_better": True,
             "scaling": "weak",

@@ -19,9 +19,9 @@ if [ -z "$SKIP_TESTS" ]; then
   rc=$?; if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 fi
 step smoke 200 python __graft_entry__.py smoke || exit $?
-TAIL=1 step bench 400 python bench.py || exit $?
+TAIL=1 step bench 400 python bench.py --full || exit $?
 step rocprof 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/gpurun_out/prof" -o run -- \
-    python3 "$R/bench.py" --steps 5 --warmup 2 --cpu-seconds 0 || exit $?
+    python3 "$R/bench.py" --full --steps 5 --warmup 2 --cpu-seconds 0 || exit $?
 for c in FETCH_SIZE WRITE_SIZE; do
   step pmc_$c 300 rocprofv3 --pmc $c --output-format csv -d "$R/gpurun_out/pmc/$c" -o run -- \
       python3 "$R/bench.py" --steps 2 --warmup 1 --cpu-seconds 0 --no-verify || exit $?
