@@ -130,8 +130,9 @@ int rs_reconstruct_batch_dev(uint64_t original_count, uint64_t recovery_count, s
 
 /* Reconstruct with a per-stripe erasure pattern (§8f rank 2). d_present: DEVICE
  * array, n_stripes rows of k+m flags (row stride present_stride, 0 = k+m). The
- * erasure locator (Generic.zig:200-215, two 64K-point FWHTs) is evaluated per
- * stripe on the GPU. Stripe s restores its missing originals, ascending, into
+ * erasure locator (Generic.zig:200-215) is evaluated per stripe on the GPU: a small
+ * erased set's log terms are summed point by point, only large sets take the two
+ * 64K-point FWHTs. Stripe s restores its missing originals, ascending, into
  * slots [0, e_s) of its d_restored row ([n][max_e][shard_bytes]); slots >= e_s
  * are not written. d_status (device, n int32, may be NULL) receives per stripe
  * RS_OK, RS_ERR_NOT_ENOUGH_SHARDS (< k present) or RS_ERR_INVALID_ARGUMENT
@@ -145,18 +146,15 @@ int rs_reconstruct_batch_dev_patterns(uint64_t original_count, uint64_t recovery
 
 /* -------------------------------------- host-resident batches (end to end)
  * Same layouts and semantics as the *_dev calls, but the batch lives in HOST
- * memory: the library streams it through HBM in slices on a 2-slot (RS_AMD_HOST_SLOTS)
+ * memory: the library streams it through HBM in slices on a 2-slot
  * H2D -> kernel -> D2H pipeline on its own streams (PCIe full duplex overlapped
  * with compute) and returns when the results are in host memory. Pinned host
  * buffers (hipHostMalloc / hipHostRegister / torch pin_memory) run at PCIe rate;
- * pageable buffers are copied by host threads (up to 16, RS_AMD_HOST_THREADS) through the
- * ring's own pinned staging (RS_AMD_HOST_STAGE=0: the HIP runtime's pageable path instead).
+ * pageable buffers are copied by host threads through the ring's own pinned staging.
  * A reconstruct reads only the present shards: one copy per run of consecutive present
- * rows (RS_AMD_HOST_GAP=n also copies gaps of up to n missing rows, bytes never read),
- * in slices of 256 MiB (RS_AMD_HOST_SLICE_MB) widened up to 1 GiB while the narrowest
- * run's copy would move less than 8 MiB. Ring copies use the 2D copy form (faster than the
- * 1D one from pinned memory; RS_AMD_HOST_COPY2D=0 reverts). The ring's device buffers persist
- * per device. */
+ * rows, in slices of 256 MiB widened up to 1 GiB while the narrowest run's copy would
+ * move less than 8 MiB. Ring copies use the 2D copy form (faster than the 1D one from
+ * pinned memory). The ring's device buffers persist per device. Knobs: Environment, below. */
 int rs_encode_batch_host(uint64_t original_count, uint64_t recovery_count, size_t shard_bytes, uint64_t n_stripes,
                          const void *h_original, uint64_t original_stripe_stride, void *h_recovery,
                          uint64_t recovery_stripe_stride, uint32_t flags);
@@ -189,7 +187,7 @@ int rs_reconstruct_batch_host_multi(uint64_t original_count, uint64_t recovery_c
  * min(k, m) originals lost". net_<role>_* = bit-sliced XOR network (or bit-sliced FFT
  * kernel, net_fft_*) generated for the plan and compiled with hipRTC on first use (shards of
  * 1 / 2 KiB or whole 4 KiB units, <= 64 outputs; up to 64 input blocks compile in the call,
- * larger maps in the background; disable with RS_AMD_JIT=0). A prediction: the kernels a
+ * larger maps in the background). A prediction: the kernels a
  * call actually launched are in rs_last_kernels. */
 const char *rs_encode_kernel_name(uint64_t original_count, uint64_t recovery_count, size_t shard_bytes);
 const char *rs_reconstruct_kernel_name(uint64_t original_count, uint64_t recovery_count, size_t shard_bytes,
@@ -211,17 +209,16 @@ const char *rs_patterns_kernel_name(uint64_t original_count, uint64_t recovery_c
  * first calls run the fused FFT reconstruct with the pattern as data (rs_fft_decode_*,
  * nothing compiled per pattern). One steady-state kernel per pattern is then built on the
  * background worker, behind the full plan's build: a network where one beats the fused
- * kernel (few losses: the direct map, queued at the pattern's second call; RS_AMD_FDEC=0:
- * the e x e syndrome map), else the fused kernel with the pattern compiled in
+ * kernel (few losses: the direct map, queued at the pattern's second call; without the fused
+ * reconstruct: the e x e syndrome map), else the fused kernel with the pattern compiled in
  * (rs_fft_pdecode_*, k <= 256; RS(200,55): 8-16 s of hipRTC), queued at the pattern's
- * RS_AMD_PDEC_AFTER-th call (default 2). The pattern-compiled kernels are bounded: at most
- * RS_AMD_PDEC_MAX (default 32) patterns per code and device (later patterns keep the
- * pattern-as-data kernel), and none is queued while more than RS_AMD_PDEC_QUEUE (default 2)
- * jobs wait on the worker (a later call retries). The calls run the first form until the
- * steady-state kernel is loaded. rs_net_wait blocks until the worker is idle (no plan build
- * or compile queued or running): after two calls + rs_net_wait the next call runs the
- * pattern's steady-state kernel (rs_reconstruct_warm gets there at once). RS_AMD_JIT_SYNC=1
- * compiles in the calling thread instead. Returns RS_OK. */
+ * second call. The pattern-compiled kernels are bounded: at most 32 patterns per code and
+ * device (later patterns keep the pattern-as-data kernel), and none is queued while more
+ * than 2 jobs wait on the worker (a later call retries). The calls run the first form until
+ * the steady-state kernel is loaded. rs_net_wait blocks until the worker is idle (no plan
+ * build or compile queued or running): after two calls + rs_net_wait the next call runs the
+ * pattern's steady-state kernel (rs_reconstruct_warm gets there at once). The counts are
+ * knobs: Environment, below. Returns RS_OK. */
 int rs_net_wait(void);
 
 /* Drive one erasure pattern of rs_reconstruct_batch_dev (same arguments) to its steady
@@ -259,14 +256,13 @@ int rs_debug_release_caches(uint64_t *pooled_contexts);
  * positions below ceilPow2(C + k) (low: ceilPow2(C + m)) where they differ mod 65535; -1 on
  * invalid arguments. Host only, no device. */
 int64_t rs_debug_erasure_logs_check(uint64_t k, uint64_t m, const uint8_t *received, int low);
-/* Measurement builds of the FFT kernels (RS_AMD_FFT_DEBUG bit 6, rs_fftnet.cpp): every wave
+/* Measurement builds of the FFT kernels (rs_fftnet.cpp debug_of, bit 6): every wave
  * of workgroup 0 stamps s_memtime around each barrier of its third unit; copies the current
  * device's 8 x 64 stamps (wave-major) to out[0, min(n, 512)). */
 int rs_debug_fft_stamps(uint64_t *out, uint64_t n);
 
 /* hipRTC activity of this process: kernels compiled, code objects found in the on-disk
- * cache ($RS_AMD_CACHE_DIR, else $XDG_CACHE_HOME/rs_amd or ~/.cache/rs_amd; empty = off),
- * modules loaded. Any pointer may be NULL. */
+ * cache, modules loaded. Any pointer may be NULL. */
 int rs_jit_stats(uint64_t *compiles, uint64_t *cache_hits, uint64_t *modules);
 
 /* Plan-time network kernel: generate the bit-sliced network of an encode (present
@@ -345,6 +341,51 @@ const uint16_t *rs_table_log_walsh(void); /* [65536] */
  * pshufb nibble tables (8 MiB, built on the first call; the GPU kernels use their own
  * v_perm / bit-sliced forms). NULL if it cannot be allocated. */
 const uint8_t *rs_table_mul_128(void);
+
+/* ------------------------------------------------------------------ Environment
+ * The variables a user of the library may set (the public rows of the table in
+ * csrc/rs_env.hpp, which lists every variable read). Each is read at every use, so a change
+ * takes effect on the next call. Unset or empty means the default. A number outside its
+ * range is clamped to it. A flag is off only for a number equal to 0 and on for any other
+ * value.
+ *   RS_AMD_CACHE_DIR
+ *       directory of the on-disk code-object cache; empty: no disk cache; unset:
+ *       $XDG_CACHE_HOME/rs_amd or ~/.cache/rs_amd
+ *   RS_AMD_FDEC
+ *       0: never the fused FFT reconstruct; 1: whenever it applies, and no pattern-
+ *       compiled kernels; anything else: auto
+ *   RS_AMD_HOST_SLICE_MB (1.., default computed)
+ *       input MiB per host-batch slice; unset: 256, and reconstructs widen it for narrow
+ *       row runs
+ *   RS_AMD_HOST_SLOTS (1..8, default 2)
+ *       slices in flight in the host-batch ring
+ *   RS_AMD_HOST_STAGE (flag, default on)
+ *       0: pageable host buffers go to the runtime as they are, without the ring's
+ *       pinned staging
+ *   RS_AMD_HOST_THREADS (1..64, default computed)
+ *       host threads of the staging copies; unset: min(16, hardware threads)
+ *   RS_AMD_JIT (flag, default on)
+ *       0: no hipRTC kernels at all, every call runs on the precompiled table kernels
+ *   RS_AMD_JIT_CACHE_MAX (0.., default 1024)
+ *       loaded hipRTC modules per process; past it new maps run on the table kernels
+ *   RS_AMD_JIT_SYNC (flag, default off)
+ *       1: background compiles run in the calling thread instead
+ *   RS_AMD_JIT_VERBOSE
+ *       set at all: report every compile and disk-cache hit on stderr
+ *   RS_AMD_LOW_BLOCK (flag, default on)
+ *       0: low-rate reconstructs keep the W-point decode instead of the block form
+ *   RS_AMD_PDEC (flag, default on)
+ *       0: no pattern-compiled fused reconstruct kernels
+ *   RS_AMD_PDEC_AFTER (1.., default 2)
+ *       a pattern is compiled in on its n-th use
+ *   RS_AMD_PDEC_MAX (0.., default 32)
+ *       pattern-compiled kernels per code and device
+ *   RS_AMD_PDEC_QUEUE (0.., default 2)
+ *       pattern compiles waiting on the worker before new ones are put off
+ *   RS_AMD_PLAN_CACHE (1.., default 4096)
+ *       plans kept per kind before the least recently used are dropped
+ *   RS_AMD_SCRATCH_CAP_MB (1.., default 2048)
+ *       scratch MiB per launch of the generic kernels */
 
 #ifdef __cplusplus
 }

@@ -158,10 +158,7 @@ int align_nv(std::initializer_list<uint64_t> vals) {
   return 0;
 }
 
-uint32_t async_after() {
-  const char *e = std::getenv("RS_AMD_NET_ASYNC_AFTER");
-  return e && *e ? static_cast<uint32_t>(std::max(1, std::atoi(e))) : 2u;
-}
+uint32_t async_after() { return static_cast<uint32_t>(env::num(env::NET_ASYNC_AFTER)); }
 
 // A fallback to the table kernels is reported on stderr once per distinct reason.
 void warn_once_per_reason(const char *what, const std::string &err) {
@@ -171,10 +168,7 @@ void warn_once_per_reason(const char *what, const std::string &err) {
   if (seen.insert(err.substr(0, 200)).second) std::fprintf(stderr, "%s%s\n", what, err.c_str());
 }
 
-bool fft_enabled() {
-  const char *e = std::getenv("RS_AMD_FFT");
-  return jit::enabled() && !(e && std::strcmp(e, "0") == 0);
-}
+bool fft_enabled() { return jit::enabled() && env::on(env::FFT); }
 
 // The slot's kernel for shards of sb bytes; *used = the spec to launch it with.
 const jit::Kernel *fft_kernel(FftSlot &slot, uint64_t sb, const fftnet::Spec **used) {
@@ -211,8 +205,7 @@ const jit::Kernel *net_kernel(NetSlot &slot, uint64_t sb) {
   std::string err;
   bool pending = false;
   if (slot.async && slot.uses < async_after()) {  // a one-off pattern is not worth a background compile
-    const char *sync = std::getenv("RS_AMD_JIT_SYNC");
-    if (!(sync && *sync && std::strcmp(sync, "0") != 0) && ++slot.uses < async_after()) return nullptr;
+    if (!env::on(env::JIT_SYNC) && ++slot.uses < async_after()) return nullptr;
   }
   jit::NetSpec small;
   if (pieces > 1) {

@@ -11,6 +11,7 @@
 #include <sstream>
 
 #include "reedsol.h"
+#include "rs_env.hpp"
 #include "rs_gf.hpp"
 #include "rs_internal.hpp"
 
@@ -339,26 +340,20 @@ __device__ __forceinline__ void rmul(u32 *x, cptr M, const Km KM) {
 }
 )HIP";
 
-int env_int(const char *name, int def) {
-  const char *e = std::getenv(name);
-  return e && *e ? std::atoi(e) : def;
-}
-
-
 // butterflies between sched_barriers: 0 / 2 / 4 measured the same as 1 (RS(200,55) encode
 // 3.72 / 3.70 / 3.72 vs 3.69 ms, fused decode 6.86 / 6.89 / 6.89 vs 6.90 ms,
 // profiles/r03/negative/fft_sched_spacing.jsonl); 1 bounds the compile time
 int sched_of() { return 1; }
 
 int prefetch_of(const Spec &s) {
-  return std::max(0, std::min(8, s.prefetch >= 0 ? s.prefetch : env_int("RS_AMD_FFT_PREFETCH", 4)));
+  return std::max(0, std::min(8, s.prefetch >= 0 ? s.prefetch : env::num(env::FFT_PREFETCH)));
 }
 
 // RS_AMD_FFT_DEBUG (measurement builds only, part of the cache key): bit 0 loads read
 // through the zero-record resource (no HBM reads), bit 1 stores dropped the same way, bit 2
 // decode kernels stop after Enc(d') (no decode tail), bit 3 decode: no runtime multiplies,
 // bit 4 decode: the round-3 load order (rec rows loaded at the tail, no prefetch)
-int debug_of() { return env_int("RS_AMD_FFT_DEBUG", 0); }
+int debug_of() { return env::num(env::FFT_DEBUG); }
 
 // the stamp buffer of measurement builds (8 waves x 64 u64 per device)
 std::mutex g_stamp_mu;
@@ -370,30 +365,14 @@ unsigned long long *stamp_buffer(int dev) {
   return p;
 }
 
-// Spec::present: where a wave's rows of R are loaded (RS_AMD_PDEC_RLOAD): 0 at the start of its
-// syndrome branch (round 4), 1 at the start of its final-FFT A layers (in flight during them),
-// 2 before the final FFT's B layers (round 4's dbg bit 5), 3 half at 1, half at 0
-int rload_of() {
-  const int v = env_int("RS_AMD_PDEC_RLOAD", 0);
-  return v >= 0 && v <= 3 ? v : 0;
-}
-
-// unit walk (RS_AMD_FFT_WALK): 1 = blocked (workgroup b takes units [b per, (b + 1) per): a
-// stripe's 2 KiB column slices in order, each shard row streamed sequentially by one CU),
-// 0 = interleaved (units b, b + grid, ...: every CU on the same two stripes at once)
-int walk_of() { return env_int("RS_AMD_FFT_WALK", 0) ? 1 : 0; }
-
-// the transpose / basis masks in VGPRs (RS_AMD_FFT_VMASK, default on)
-int vmask_of() { return env_int("RS_AMD_FFT_VMASK", 1) ? 1 : 0; }
-
-// runtime-multiply output planes per scalar-load step (RS_AMD_FFT_RMULG: 1, 2, 4, 8). 4: per-stripe
-// RS(200,55) max_e 55 7.35 -> 6.66 ms, RS(16,16) 2.79 -> 2.71 ms (profiles/r04/patterns/rmul_ab.log).
+// Code shapes measured and fixed (DESIGN.md §"The kernels do not follow it"): the unit walk is
+// interleaved (units b, b + grid, ...) unless the Spec asks for the blocked one; a
+// pattern-compiled kernel loads a wave's rows of R at the start of its syndrome branch; the
+// transpose / basis masks live in VGPRs; the runtime multiply takes 4 output planes per
+// scalar-load step (per-stripe RS(200,55) max_e 55 7.35 -> 6.66 ms, RS(16,16) 2.79 -> 2.71 ms,
+// profiles/r04/patterns/rmul_ab.log; the prelude's RS_RMUL_G is only ever generated as 4).
 // Measured and removed: the masks through vector loads (7.35 -> 8.9 ms), s_setprio turns
 // between the SIMD-pair halves (c4 neutral to 8 % slower, profiles/r04/prio1.log)
-int rmul_group() {
-  const int g = env_int("RS_AMD_FFT_RMULG", 4);
-  return g == 2 || g == 4 || g == 8 ? g : 1;
-}
 
 struct Gen {
   std::ostringstream o;
@@ -669,7 +648,7 @@ std::string gen_source(const Spec &s, const std::string &name, Stats *stats) {
   }
   o << "#define RS_AUX_LD 2\n#define RS_AUX_ST 2\n#define RS_STAMPS " << ((dbg & 64) ? 1 : 0) << "\n"
     << (s.decode && (dbg & 8) ? "#define RS_DBG_NORMUL 1\n" : "")
-    << "#define RS_RMUL_G " << rmul_group() << "\n" << kPrelude;
+    << "#define RS_RMUL_G 4\n" << kPrelude;
   // 1 KiB shards (pieces 2): a unit's two 1 KiB halves are the same slice of stripes
   // 2u and 2u + 1 (resources R* and R*1; the second is the zero-record RZ past the
   // batch, so its loads read zeros and its stores are dropped)
@@ -703,7 +682,7 @@ std::string gen_source(const Spec &s, const std::string &name, Stats *stats) {
     << "  __shared__ u32 xch[" << C * 8 * 64 << "];\n"
     << "  v4 *const xch4 = (v4 *)xch;\n"
     << "  Km KM = {0x0F0F0F0Fu, 0x33333333u, 0x55555555u};\n"
-    << (vmask_of() ? "  asm volatile(\"\" : \"+v\"(KM.f), \"+v\"(KM.t), \"+v\"(KM.s));\n" : "")
+    << "  asm volatile(\"\" : \"+v\"(KM.f), \"+v\"(KM.t), \"+v\"(KM.s));\n"
     << "  const u32 lane = threadIdx.x & 63u, ll = lane & 31u;\n"
        "  const u32 w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);\n"
        "  const u32 loff = (ll >> 1) * 64u + (lane >= 32u ? 32u : 0u) + (ll & 1u) * 16u;\n"
@@ -929,33 +908,8 @@ std::string gen_source(const Spec &s, const std::string &name, Stats *stats) {
         << " = LDB(us" << r << " ? RR : RZ, uo, pd" << r << " * sbl), rb" << r << " = LDB(us" << r
         << " ? RR1 : RZ, uo1, pd" << r << " * sbl);\n";
   };
-  // Spec::present: a wave's rows of R (static), loaded where RS_AMD_PDEC_RLOAD says; r0..r1 of them
-  const int rload = spat ? ((dbg & 32) ? 2 : rload_of()) : 0;
-  auto emit_rows_R = [&](uint32_t w, uint32_t r0, uint32_t r1) {
-    for (uint32_t r = r0; r < r1; r++) {
-      const uint32_t p = P.posA(w, r);
-      if (p < s.m && inR[p])
-        o << "  ra" << r << " = LDB(RR, uo, " << p << "u * sbl); rb" << r << " = LDB(RR1, uo1, " << p << "u * sbl);\n";
-    }
-  };
-  if (tail && rload) {
-    o << "  v4 ";
-    for (uint32_t r = 0; r < 8; r++) o << "ra" << r << ", rb" << r << (r < 7 ? ", " : ";\n");
-  }
-  if (tail && rload == 2) {  // before the final FFT's B layers (round 4 measured: spills)
-    bool firstw = true;
-    for (uint32_t w = 0; w < NW; w++) {
-      bool any = false;
-      for (uint32_t r = 0; r < 8; r++) any |= P.posA(w, r) < s.m && inR[P.posA(w, r)];
-      if (!any) continue;
-      o << "  " << (firstw ? "if" : "else if") << " (w == " << w << "u) {\n";
-      firstw = false;
-      emit_rows_R(w, 0, 8);
-      o << "  }\n";
-    }
-  } else if (tail && !old_order && !spat) {
-    emit_rec_loads();
-  }
+  // (Spec::present: a wave's rows of R are static and loaded in its syndrome branch, below)
+  if (tail && !old_order && !spat) emit_rec_loads();
   o << "  // ---- FFT(size " << C << ", trunc " << s.m << ", skew_delta 0), Generic.zig:15-78\n";
   g.ops = &g.st->ops_b;
   bool zc[8];
@@ -1005,13 +959,8 @@ std::string gen_source(const Spec &s, const std::string &name, Stats *stats) {
     return anyout;
   };
   // a wave's A layers of the final FFT; the decode kernels keep Enc(d') rows p < m in registers
-  // for the tail (Spec::present: emitted inside the tail's per-wave branch, below, with the
-  // wave's rows of R in flight during them when RS_AMD_PDEC_RLOAD is 1 or 3)
+  // for the tail (Spec::present: emitted inside the tail's per-wave branch, below)
   auto final_A = [&](uint32_t w, std::vector<uint8_t> &zout) {
-    if (tail && (rload == 1 || rload == 3)) {  // this wave's rows of R, in flight during its A layers
-      emit_rows_R(w, 0, rload == 1 ? 8 : 4);
-      o << "  asm volatile(\"\" ::: \"memory\");\n  __builtin_amdgcn_sched_barrier(0);\n";
-    }
     g.ops = &g.st->ops_a;
     bool z[8];
     for (uint32_t r = 0; r < 8; r++) {
@@ -1116,12 +1065,10 @@ std::string gen_source(const Spec &s, const std::string &name, Stats *stats) {
         final_A(w, zv);
         o << "  __builtin_amdgcn_sched_barrier(0);\n";
       }
-      if (!rload)  // this wave's rows of R, in flight together
-        for (uint32_t r = 0; r < 8; r++)
-          if (!z0[w][r])
-            o << "  const v4 ra" << r << " = LDB(RR, uo, " << P.posA(w, r) << "u * sbl), rb" << r << " = LDB(RR1, uo1, "
-              << P.posA(w, r) << "u * sbl);\n";
-      if (rload == 3) emit_rows_R(w, 4, 8);
+      for (uint32_t r = 0; r < 8; r++)  // this wave's rows of R, in flight together
+        if (!z0[w][r])
+          o << "  const v4 ra" << r << " = LDB(RR, uo, " << P.posA(w, r) << "u * sbl), rb" << r << " = LDB(RR1, uo1, "
+            << P.posA(w, r) << "u * sbl);\n";
       bool z[8];
       for (uint32_t r = 0; r < 8; r++) {
         z[r] = z0[w][r];
@@ -1492,9 +1439,8 @@ bool supports_inverse(uint64_t k, uint64_t m, uint64_t shard_bytes) {
 
 std::string cache_key(const Spec &s) {
   // code-shape knobs are part of the key (read when the source is generated)
-  std::string k = "fft4:p" + std::to_string(prefetch_of(s)) + (s.decode && !s.present.empty() && rload_of() ? ":rl" + std::to_string(rload_of()) : "") + ":s" + std::to_string(sched_of()) + ":d" +
-                  std::to_string(debug_of()) + ":g" + std::to_string(rmul_group()) + ":k" + std::to_string(vmask_of()) + ":" +
-                  std::to_string(s.k) + ":" +
+  std::string k = "fft4:p" + std::to_string(prefetch_of(s)) + ":s" + std::to_string(sched_of()) + ":d" +
+                  std::to_string(debug_of()) + ":g4:k1:" + std::to_string(s.k) + ":" +
                   std::to_string(s.m) + ":" + std::to_string(s.flags) + ":" +
                   (s.pieces > 1 ? "p" + std::to_string(s.pieces) + ":" : "") + (s.inverse ? "inv:" : "") +
                   (s.dyn ? "dyn:" : "") + (s.decode ? "dec:" : "") + (s.blocked ? "blk:" : "");
@@ -1636,7 +1582,6 @@ Stats stats(const Spec &s) {
 const jit::Kernel *get(const Spec &s, bool async, std::string &err, bool &pending) {
   Spec copy = s;
   copy.prefetch = prefetch_of(s);
-  copy.blocked = copy.blocked || walk_of();
   for (;;) {
     const std::string name = kernel_name(copy);
     const jit::Kernel *k =
@@ -1645,7 +1590,7 @@ const jit::Kernel *get(const Spec &s, bool async, std::string &err, bool &pendin
     int local = 0;
     if (hipFuncGetAttribute(&local, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k->fn) != hipSuccess) local = 0;
     // RS_AMD_FFT_ALLOW_SPILL=1: run a spilled build (tools/spill_repro.py, spill_root_cause.md)
-    if (local && std::getenv("RS_AMD_FFT_ALLOW_SPILL")) return k;
+    if (local && env::given(env::FFT_ALLOW_SPILL)) return k;
     if (local == 0 || copy.prefetch == 0) {
       // a decode kernel of a long code (RS(1000,64): 16 blocks) may keep a few registers
       // in scratch even without prefetch; since the store-data hazard fix such builds are
@@ -1663,12 +1608,7 @@ const jit::Kernel *get(const Spec &s, bool async, std::string &err, bool &pendin
 bool compile_check(const Spec &s, std::string &err, double *ms, size_t *code_bytes) {
   const std::string name = kernel_name(s);
   const std::string src = generate(s, name);
-  if (const char *dir = std::getenv("RS_AMD_JIT_DUMP")) {
-    if (FILE *f = std::fopen((std::string(dir) + "/" + name + ".hip").c_str(), "w")) {
-      std::fputs(src.c_str(), f);
-      std::fclose(f);
-    }
-  }
+  jit::dump_source(name, src);
   return jit::compile_source_check(src, err, ms, code_bytes);
 }
 

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/reedsol.h"
+#include "rs_env.hpp"
 #include "rs_fftnet.hpp"
 #include "rs_gf.hpp"
 #include "rs_internal.hpp"
@@ -190,10 +191,7 @@ struct DecodePlan {
 // kind) are dropped (a plan in use stays alive through its shared_ptr). g_plan_mu
 // guards the maps only: plans are built without it (double-checked insertion; two
 // threads racing on a new key may both build, the first insert wins).
-inline size_t plan_cache_cap() {
-  const char *e = std::getenv("RS_AMD_PLAN_CACHE");
-  return e && *e ? static_cast<size_t>(std::max(1, std::atoi(e))) : 4096u;
-}
+inline size_t plan_cache_cap() { return static_cast<size_t>(env::num(env::PLAN_CACHE)); }
 
 template <class V>
 struct PlanCache {
@@ -240,11 +238,9 @@ int upload(const void *host, size_t bytes, int dev, std::shared_ptr<DevBuf> &out
 int twiddle_plan(int dev, uint64_t W, uint32_t flags, std::shared_ptr<DevBuf> &out, size_t &off_fft);
 
 constexpr uint64_t kScratchCap = 2ull << 30;  // generic path: scratch per launch
+static_assert(env::kTable[env::SCRATCH_CAP_MB].def == kScratchCap >> 20, "the knob's default is kScratchCap");
 // the generic kernels' scratch cap per launch: kScratchCap, or RS_AMD_SCRATCH_CAP_MB
-inline uint64_t scratch_cap() {
-  const char *e = std::getenv("RS_AMD_SCRATCH_CAP_MB");
-  return e && *e ? std::max<uint64_t>(1, std::strtoull(e, nullptr, 10)) << 20 : kScratchCap;
-}
+inline uint64_t scratch_cap() { return static_cast<uint64_t>(env::num(env::SCRATCH_CAP_MB)) << 20; }
 // stripes per scratch slice: as many as fit the cap, spread evenly over the slices (a short
 // last slice runs its launches at lower occupancy)
 inline uint64_t slice_stripes(uint64_t n, uint64_t per_stripe_bytes) {

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "rs_host.hpp"
+#include "rs_host_ring.hpp"
 
 using namespace rs;
 using namespace rs::host;
@@ -21,16 +22,10 @@ namespace {
 // Copy `rows` rows of `row_bytes` between (possibly strided) buffers, always in the 2D form: for
 // pinned host memory it moves contiguous slices faster than hipMemcpyAsync does (RS(10,4) 1 MiB
 // encode 41.5 -> 52.3 GiB/s of data, 62 -> 79 GB/s over PCIe; c4 encode 44.6 -> 52.4;
-// profiles/r06/e2e/copy2d/). RS_AMD_HOST_COPY2D=0 sends contiguous copies as hipMemcpyAsync.
-bool copy_2d_always() {
-  const char *e = std::getenv("RS_AMD_HOST_COPY2D");
-  return !(e && *e == '0');
-}
+// profiles/r06/e2e/copy2d/).
 hipError_t copy_rows(void *dst, uint64_t dst_stride, const void *src, uint64_t src_stride, uint64_t row_bytes,
                      uint64_t rows, hipMemcpyKind kind, hipStream_t s) {
   if (rows == 0 || row_bytes == 0) return hipSuccess;
-  if (dst_stride == row_bytes && src_stride == row_bytes && !copy_2d_always())
-    return hipMemcpyAsync(dst, src, rows * row_bytes, kind, s);
   return hipMemcpy2DAsync(dst, dst_stride, src, src_stride, row_bytes, rows, kind, s);
 }
 
@@ -38,10 +33,6 @@ hipError_t copy_rows(void *dst, uint64_t dst_stride, const void *src, uint64_t s
 // on): host threads copy a slice's rows into it while the previous slice is on PCIe, and the
 // device copies run from pinned memory in the 2D form; the runtime's own pageable path stages
 // through a smaller buffer one copy at a time.
-bool host_stage_on() {
-  const char *e = std::getenv("RS_AMD_HOST_STAGE");
-  return !(e && *e == '0');
-}
 bool is_pinned(const void *p) {
   hipPointerAttribute_t a;
   if (hipPointerGetAttributes(&a, p) != hipSuccess) {
@@ -51,51 +42,13 @@ bool is_pinned(const void *p) {
   return a.type == hipMemoryTypeHost || a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged ||
          a.type == hipMemoryTypeUnified;
 }
-int stage_threads() {
-  const char *e = std::getenv("RS_AMD_HOST_THREADS");
-  const int hw = static_cast<int>(std::thread::hardware_concurrency());
-  return e && *e ? std::max(1, std::min(64, std::atoi(e))) : std::max(1, std::min(16, hw));
-}
-// strided host-to-host copies (rows of `w` bytes), split into <= 4 MiB pieces over host threads
-struct CopyJob {
-  uint8_t *d;
-  uint64_t ds;
-  const uint8_t *s;
-  uint64_t ss, w, rows;
-};
-void host_copy(const std::vector<CopyJob> &jobs) {
-  struct Piece {
-    uint8_t *d;
-    const uint8_t *s;
-    uint64_t len;
-  };
-  std::vector<Piece> pieces;
-  for (const CopyJob &j : jobs)
-    for (uint64_t r = 0; r < j.rows; r++)
-      for (uint64_t o = 0; o < j.w; o += 4ull << 20)
-        pieces.push_back({j.d + r * j.ds + o, j.s + r * j.ss + o, std::min<uint64_t>(4ull << 20, j.w - o)});
-  const int T = static_cast<int>(std::min<uint64_t>(static_cast<uint64_t>(stage_threads()), pieces.size()));
-  auto work = [&](int t) {
-    for (size_t i = static_cast<size_t>(t); i < pieces.size(); i += static_cast<size_t>(T))
-      std::memcpy(pieces[i].d, pieces[i].s, pieces[i].len);
-  };
-  if (T <= 1) {
-    if (T == 1) work(0);
-    return;
-  }
-  std::vector<std::thread> th;
-  th.reserve(T - 1);
-  for (int t = 1; t < T; t++) th.emplace_back(work, t);
-  work(0);
-  for (auto &x : th) x.join();
-}
 
 // Per-device staging ring of the host-batch calls: `slots` slices, each on its own
 // stream (H2D -> kernel -> D2H in order; slices on different streams overlap both
 // PCIe directions with the kernels). Buffers and streams persist across calls and
 // grow on demand; the ring's mutex serialises host-batch calls on one device.
 struct Pipeline {
-  static constexpr int kMaxSlots = 8;
+  static constexpr int kMaxSlots = 8;  // the upper bound of RS_AMD_HOST_SLOTS (rs_env.hpp)
   std::mutex mu;
   int slots = 0;  // ring depth in use (RS_AMD_HOST_SLOTS, default 2)
   hipStream_t st[kMaxSlots] = {};
@@ -145,64 +98,13 @@ struct Pipeline {
     return RS_OK;
   }
 };
-
-// ring shape (env, read per call): RS_AMD_HOST_SLOTS (1..8, default 2) slices of
-// RS_AMD_HOST_SLICE_MB input MiB (default 256). Pinned RS(10,4) 1 MiB x 512 encode /
-// reconstruct GiB/s: 1 slot 37.5 / 37.0, 2 slots 49.3 / 49.8, 3 slots 44.6 / 48.8,
-// 6 x 64 MiB 46.4 / 46.2 (profiles/r01/e2e_shapes): two slices keep one H2D, one
-// kernel and one D2H in flight; more streams only contend for the copy engines.
-int host_slots() {
-  const char *e = std::getenv("RS_AMD_HOST_SLOTS");
-  return e && *e ? std::max(1, std::min(Pipeline::kMaxSlots, std::atoi(e))) : 2;
-}
-// A slice's present shards cross PCIe as one strided copy per run of present rows; a run
-// bridges gaps of up to RS_AMD_HOST_GAP missing rows (their bytes are copied too and never
-// read: the caller's arrays hold every row); -1: one copy per row (round 5, measurement
-// baseline). Measured: DESIGN.md §6 e2e.
-int64_t host_gap_rows() {
-  const char *e = std::getenv("RS_AMD_HOST_GAP");
-  return e && *e ? std::max(-1, std::atoi(e)) : 0;
-}
-// [first, last) runs of present[0, rows) with gaps of <= gap missing rows bridged
-std::vector<std::pair<uint64_t, uint64_t>> present_runs(const uint8_t *present, uint64_t rows, int64_t gap) {
-  std::vector<std::pair<uint64_t, uint64_t>> runs;
-  for (uint64_t j = 0; j < rows; j++) {
-    if (!present[j]) continue;
-    if (!runs.empty() && gap >= 0 && j - runs.back().second <= static_cast<uint64_t>(gap))
-      runs.back().second = j + 1;
-    else
-      runs.emplace_back(j, j + 1);
-  }
-  return runs;
-}
-uint64_t host_slice_bytes() {
-  const char *e = std::getenv("RS_AMD_HOST_SLICE_MB");
-  return (e && *e ? static_cast<uint64_t>(std::max(1, std::atoi(e))) : 256ull) << 20;
-}
-// Stripes per reconstruct slice: the default 256 MiB, widened (up to 1 GiB) until the narrowest
-// run's copy moves >= 8 MiB — c4 with every third data shard lost copies 2-row runs of 256 KiB
-// shards: 46.7 / 48.9 / 49.3 GiB/s at 256 / 512 / 1024 MiB slices, where RS(10,4)'s 6-row runs of
-// 1 MiB shards want 256 (50.0 / 49.3 / 47.8; profiles/r06/e2e/slice/). RS_AMD_HOST_SLICE_MB fixes it.
-uint64_t reconstruct_slice_stripes(uint64_t n, uint64_t stripe_bytes, uint64_t sb,
-                                   const std::vector<std::pair<uint64_t, uint64_t>> &runs) {
-  uint64_t S = std::max<uint64_t>(1, host_slice_bytes() / stripe_bytes);
-  const char *e = std::getenv("RS_AMD_HOST_SLICE_MB");
-  if (!(e && *e)) {
-    uint64_t narrow = UINT64_MAX;
-    for (const auto &r : runs) narrow = std::min(narrow, (r.second - r.first) * sb);
-    if (narrow != UINT64_MAX) {
-      const uint64_t want = ((8ull << 20) + narrow - 1) / narrow;
-      S = std::max(S, std::min(want, std::max<uint64_t>(1, (1ull << 30) / stripe_bytes)));
-    }
-  }
-  return std::min(S, n);
-}
+static_assert(env::kTable[env::HOST_SLOTS].hi == Pipeline::kMaxSlots, "RS_AMD_HOST_SLOTS is clamped to the ring's slots");
 
 // Fault injection for the error-path test (the reference's checkAllAllocationFailures,
 // tests.zig:131-156, in spirit): RS_AMD_INJECT_HOST_FAIL=i fails slice i of a host batch.
 bool inject_host_failure(uint64_t slice) {
-  const char *e = std::getenv("RS_AMD_INJECT_HOST_FAIL");
-  return e && *e && std::strtoull(e, nullptr, 10) == slice;
+  const int i = env::num(env::INJECT_HOST_FAIL);
+  return i != env::kAuto && static_cast<uint64_t>(i) == slice;
 }
 
 // process-lifetime rings (never freed: the HIP runtime reclaims them at exit)
@@ -217,6 +119,99 @@ struct Pipelines {
     return *p;
   }
 };
+
+// What a host batch moves per slice of stripes. Ring buffer j holds rows[j] shard rows per
+// stripe (originals, recovery, restored). `In`: shard rows [first, last) of buffer `buf` come
+// from the caller's array at `host` (stripes `stride` bytes apart); `Out`: all of buffer `buf`
+// goes back to the caller.
+struct In {
+  int buf;
+  uint64_t first, last;
+  const uint8_t *host;
+  uint64_t stride;
+};
+struct Out {
+  int buf;
+  uint8_t *host;
+  uint64_t stride;
+};
+
+// The slice loop of both host batches: n stripes in slices of S through the device's ring
+// (RS_AMD_HOST_SLOTS slices in flight, read per call). Pinned RS(10,4) 1 MiB x 512 encode /
+// reconstruct GiB/s: 1 slot 37.5 / 37.0, 2 slots 49.3 / 49.8, 3 slots 44.6 / 48.8,
+// 6 x 64 MiB 46.4 / 46.2 (profiles/r01/e2e_shapes): two slices keep one H2D, one
+// kernel and one D2H in flight; more streams only contend for the copy engines.
+// kernel(cnt, bufs, stream) runs one slice on the slot's device buffers.
+template <class K>
+int run_ring(int dev, uint64_t n, uint64_t S, uint64_t sb, const uint64_t (&rows)[3], bool pinned,
+             const std::vector<In> &in, const Out &out, K &&kernel) {
+  const int slots = env::num(env::HOST_SLOTS);
+  Pipeline &p = Pipelines::of(dev);
+  std::lock_guard<std::mutex> lk(p.mu);
+  const uint64_t bytes[3] = {S * rows[0] * sb, S * rows[1] * sb, S * rows[2] * sb};
+  int st = p.ensure(bytes, slots);
+  if (st) return st;
+  const bool stage = env::on(env::HOST_STAGE) && !pinned;
+  if (stage && (st = p.ensure_stage(bytes, slots))) return st;
+  const uint64_t out_bytes = rows[out.buf] * sb;
+  uint64_t pend_s0[Pipeline::kMaxSlots] = {}, pend_cnt[Pipeline::kMaxSlots] = {};
+  // staged: a slot's previous slice is waited for and its output copied out before the slot's
+  // staging buffers take the next slice
+  auto take_out = [&](int slot) {
+    if (!pend_cnt[slot]) return;
+    host_copy({{out.host + pend_s0[slot] * out.stride, out.stride, static_cast<const uint8_t *>(p.hst[slot][out.buf]),
+                out_bytes, out_bytes, pend_cnt[slot]}});
+    pend_cnt[slot] = 0;
+  };
+  auto slices = [&]() -> int {
+    for (uint64_t s0 = 0, i = 0; s0 < n; s0 += S, i++) {
+      const int slot = static_cast<int>(i % static_cast<uint64_t>(slots));
+      const uint64_t cnt = std::min(S, n - s0);
+      hipStream_t q = p.st[slot];
+      if (inject_host_failure(i)) return fail(RS_ERR_DEVICE, "injected host-batch failure");
+      if (stage) {  // the rows into the slot's staging, in the device layout
+        HIP_TRY(hipStreamSynchronize(q));
+        take_out(slot);
+        std::vector<CopyJob> jobs;
+        for (const In &r : in)
+          jobs.push_back({static_cast<uint8_t *>(p.hst[slot][r.buf]) + r.first * sb, rows[r.buf] * sb,
+                          r.host + s0 * r.stride + r.first * sb, r.stride, (r.last - r.first) * sb, cnt});
+        host_copy(jobs);
+      }
+      for (const In &r : in) {  // one copy per run of rows
+        const uint8_t *src = stage ? static_cast<const uint8_t *>(p.hst[slot][r.buf]) : r.host + s0 * r.stride;
+        HIP_TRY(copy_rows(static_cast<uint8_t *>(p.buf[slot][r.buf]) + r.first * sb, rows[r.buf] * sb,
+                          src + r.first * sb, stage ? rows[r.buf] * sb : r.stride, (r.last - r.first) * sb, cnt,
+                          hipMemcpyHostToDevice, q));
+      }
+      const int rc = kernel(cnt, p.buf[slot], q);
+      if (rc) return rc;
+      if (stage) {
+        HIP_TRY(copy_rows(p.hst[slot][out.buf], out_bytes, p.buf[slot][out.buf], out_bytes, out_bytes, cnt,
+                          hipMemcpyDeviceToHost, q));
+        pend_s0[slot] = s0;
+        pend_cnt[slot] = cnt;
+      } else {
+        HIP_TRY(copy_rows(out.host + s0 * out.stride, out.stride, p.buf[slot][out.buf], out_bytes, out_bytes, cnt,
+                          hipMemcpyDeviceToHost, q));
+      }
+    }
+    return RS_OK;
+  };
+  // every slot stream is drained before the call returns, after an error and before an
+  // exception leaves too: no copy into the caller's buffers (or out of them) outlives the call
+  int rc;
+  try {
+    rc = slices();
+  } catch (...) {
+    (void)p.finish();
+    throw;
+  }
+  const int fin = p.finish();
+  if (stage && fin == RS_OK)
+    for (int slot = 0; slot < slots; slot++) take_out(slot);  // slices that completed, also before an error
+  return rc ? rc : fin;
+}
 
 }  // namespace
 
@@ -261,58 +256,13 @@ int rs_encode_batch_host(uint64_t k, uint64_t m, size_t sb, uint64_t n, const vo
     if (rec_stride == 0) rec_stride = m * sb;
     int dev;
     if ((st = current_device(&dev))) return st;
-    const uint64_t S = std::max<uint64_t>(1, std::min<uint64_t>(n, host_slice_bytes() / (k * sb)));
-    const int slots = host_slots();
-    Pipeline &p = Pipelines::of(dev);
-    std::lock_guard<std::mutex> lk(p.mu);
-    const uint64_t bytes[3] = {S * k * sb, S * m * sb, 0};
-    if ((st = p.ensure(bytes, slots))) return st;
-    const bool stage = host_stage_on() && !(is_pinned(h_orig) && is_pinned(h_rec));
-    if (stage && (st = p.ensure_stage(bytes, slots))) return st;
-    uint64_t pend_s0[Pipeline::kMaxSlots] = {}, pend_cnt[Pipeline::kMaxSlots] = {};
-    // staged: a slot's previous slice is waited for and its parity copied out before the slot's
-    // staging buffers take the next slice
-    auto take_out = [&](int slot) {
-      if (!pend_cnt[slot]) return;
-      host_copy({{static_cast<uint8_t *>(h_rec) + pend_s0[slot] * rec_stride, rec_stride,
-                  static_cast<const uint8_t *>(p.hst[slot][1]), m * sb, m * sb, pend_cnt[slot]}});
-      pend_cnt[slot] = 0;
-    };
-    auto slices = [&]() -> int {
-      for (uint64_t s0 = 0, i = 0; s0 < n; s0 += S, i++) {
-        const int slot = static_cast<int>(i % static_cast<uint64_t>(slots));
-        const uint64_t cnt = std::min(S, n - s0);
-        hipStream_t q = p.st[slot];
-        if (inject_host_failure(i)) return fail(RS_ERR_DEVICE, "injected host-batch failure");
-        const uint8_t *src = static_cast<const uint8_t *>(h_orig) + s0 * orig_stride;
-        uint64_t src_stride = orig_stride;
-        if (stage) {
-          HIP_TRY(hipStreamSynchronize(q));
-          take_out(slot);
-          host_copy({{static_cast<uint8_t *>(p.hst[slot][0]), k * sb, src, orig_stride, k * sb, cnt}});
-          src = static_cast<const uint8_t *>(p.hst[slot][0]);
-          src_stride = k * sb;
-        }
-        HIP_TRY(copy_rows(p.buf[slot][0], k * sb, src, src_stride, k * sb, cnt, hipMemcpyHostToDevice, q));
-        int rc = rs_encode_batch_dev(k, m, sb, cnt, p.buf[slot][0], 0, p.buf[slot][1], 0, flags, q);
-        if (rc) return rc;
-        if (stage) {
-          HIP_TRY(copy_rows(p.hst[slot][1], m * sb, p.buf[slot][1], m * sb, m * sb, cnt, hipMemcpyDeviceToHost, q));
-          pend_s0[slot] = s0;
-          pend_cnt[slot] = cnt;
-        } else {
-          HIP_TRY(copy_rows(static_cast<uint8_t *>(h_rec) + s0 * rec_stride, rec_stride, p.buf[slot][1], m * sb,
-                            m * sb, cnt, hipMemcpyDeviceToHost, q));
-        }
-      }
-      return RS_OK;
-    };
-    // every slot stream is drained before the call returns, also after an error: no copy into
-    // the caller's buffers (or out of them) outlives the call
-    const int rc = slices(), fin = p.finish();
-    if (stage && fin == RS_OK)
-      for (int slot = 0; slot < slots; slot++) take_out(slot);  // slices that completed, also before an error
-    return rc ? rc : fin;
+    const uint64_t S =
+        std::max<uint64_t>(1, std::min<uint64_t>(n, host_slice_bytes(env::num(env::HOST_SLICE_MB)) / (k * sb)));
+    return run_ring(dev, n, S, sb, {k, m, 0}, is_pinned(h_orig) && is_pinned(h_rec),
+                    {{0, 0, k, static_cast<const uint8_t *>(h_orig), orig_stride}},
+                    {1, static_cast<uint8_t *>(h_rec), rec_stride}, [&](uint64_t cnt, void *const *b, hipStream_t q) {
+                      return rs_encode_batch_dev(k, m, sb, cnt, b[0], 0, b[1], 0, flags, q);
+                    });
   });
 }
 
@@ -335,74 +285,19 @@ int rs_reconstruct_batch_host(uint64_t k, uint64_t m, size_t sb, uint64_t n, con
     if (out_stride == 0) out_stride = e * sb;
     int dev;
     if ((st = current_device(&dev))) return st;
-    const int64_t gap = host_gap_rows();
-    const auto runs_o = present_runs(present, k, gap), runs_r = present_runs(present + k, m, gap);
-    auto runs_all = runs_o;
-    runs_all.insert(runs_all.end(), runs_r.begin(), runs_r.end());
-    const uint64_t S = reconstruct_slice_stripes(n, k * sb, sb, runs_all);
-    const int slots = host_slots();
-    Pipeline &p = Pipelines::of(dev);
-    std::lock_guard<std::mutex> lk(p.mu);
-    const uint64_t bytes[3] = {S * k * sb, S * m * sb, S * e * sb};
-    if ((st = p.ensure(bytes, slots))) return st;
-    const bool stage = host_stage_on() && !(is_pinned(h_orig) && is_pinned(h_rec) && is_pinned(h_out));
-    if (stage && (st = p.ensure_stage(bytes, slots))) return st;
-    uint64_t pend_s0[Pipeline::kMaxSlots] = {}, pend_cnt[Pipeline::kMaxSlots] = {};
-    auto take_out = [&](int slot) {
-      if (!pend_cnt[slot]) return;
-      host_copy({{static_cast<uint8_t *>(h_out) + pend_s0[slot] * out_stride, out_stride,
-                  static_cast<const uint8_t *>(p.hst[slot][2]), e * sb, e * sb, pend_cnt[slot]}});
-      pend_cnt[slot] = 0;
-    };
-    auto slices = [&]() -> int {
-      for (uint64_t s0 = 0, i = 0; s0 < n; s0 += S, i++) {
-        const int slot = static_cast<int>(i % static_cast<uint64_t>(slots));
-        const uint64_t cnt = std::min(S, n - s0);
-        hipStream_t q = p.st[slot];
-        if (inject_host_failure(i)) return fail(RS_ERR_DEVICE, "injected host-batch failure");
-        const uint8_t *so = static_cast<const uint8_t *>(h_orig) + s0 * orig_stride;
-        const uint8_t *sr = static_cast<const uint8_t *>(h_rec) + s0 * rec_stride;
-        uint64_t sos = orig_stride, srs = rec_stride;
-        if (stage) {  // the present rows into the slot's staging, in the device layout
-          HIP_TRY(hipStreamSynchronize(q));
-          take_out(slot);
-          std::vector<CopyJob> jobs;
-          uint8_t *ho = static_cast<uint8_t *>(p.hst[slot][0]), *hr = static_cast<uint8_t *>(p.hst[slot][1]);
-          for (const auto &r : runs_o)
-            jobs.push_back({ho + r.first * sb, k * sb, so + r.first * sb, orig_stride, (r.second - r.first) * sb, cnt});
-          for (const auto &r : runs_r)
-            jobs.push_back({hr + r.first * sb, m * sb, sr + r.first * sb, rec_stride, (r.second - r.first) * sb, cnt});
-          host_copy(jobs);
-          so = ho;
-          sr = hr;
-          sos = k * sb;
-          srs = m * sb;
-        }
-        // only the present shards cross PCIe (and bridged gaps), one copy per run of rows
-        for (const auto &r : runs_o)
-          HIP_TRY(copy_rows(static_cast<uint8_t *>(p.buf[slot][0]) + r.first * sb, k * sb, so + r.first * sb, sos,
-                            (r.second - r.first) * sb, cnt, hipMemcpyHostToDevice, q));
-        for (const auto &r : runs_r)
-          HIP_TRY(copy_rows(static_cast<uint8_t *>(p.buf[slot][1]) + r.first * sb, m * sb, sr + r.first * sb, srs,
-                            (r.second - r.first) * sb, cnt, hipMemcpyHostToDevice, q));
-        int rc = rs_reconstruct_batch_dev(k, m, sb, cnt, present, p.buf[slot][0], 0, p.buf[slot][1], 0,
-                                          p.buf[slot][2], 0, flags, q);
-        if (rc) return rc;
-        if (stage) {
-          HIP_TRY(copy_rows(p.hst[slot][2], e * sb, p.buf[slot][2], e * sb, e * sb, cnt, hipMemcpyDeviceToHost, q));
-          pend_s0[slot] = s0;
-          pend_cnt[slot] = cnt;
-        } else {
-          HIP_TRY(copy_rows(static_cast<uint8_t *>(h_out) + s0 * out_stride, out_stride, p.buf[slot][2], e * sb,
-                            e * sb, cnt, hipMemcpyDeviceToHost, q));
-        }
-      }
-      return RS_OK;
-    };
-    const int rc = slices(), fin = p.finish();
-    if (stage && fin == RS_OK)
-      for (int slot = 0; slot < slots; slot++) take_out(slot);
-    return rc ? rc : fin;
+    // only the present shards cross PCIe
+    std::vector<In> in;
+    for (const auto &r : present_runs(present, k))
+      in.push_back({0, r.first, r.second, static_cast<const uint8_t *>(h_orig), orig_stride});
+    for (const auto &r : present_runs(present + k, m))
+      in.push_back({1, r.first, r.second, static_cast<const uint8_t *>(h_rec), rec_stride});
+    std::vector<std::pair<uint64_t, uint64_t>> runs;
+    for (const In &r : in) runs.emplace_back(r.first, r.last);
+    const uint64_t S = reconstruct_slice_stripes(n, k * sb, sb, runs, env::num(env::HOST_SLICE_MB));
+    return run_ring(dev, n, S, sb, {k, m, e}, is_pinned(h_orig) && is_pinned(h_rec) && is_pinned(h_out), in,
+                    {2, static_cast<uint8_t *>(h_out), out_stride}, [&](uint64_t cnt, void *const *b, hipStream_t q) {
+                      return rs_reconstruct_batch_dev(k, m, sb, cnt, present, b[0], 0, b[1], 0, b[2], 0, flags, q);
+                    });
   });
 }
 

@@ -1,4 +1,4 @@
-// rs_internal.hpp — launch interface between the host codec (rs_capi.cpp) and
+// rs_internal.hpp — launch interface between the host codec (rs_host.hpp and the files behind it) and
 // the HIP kernels (rs_kernels.hip). Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -22,6 +22,7 @@
 #include <sstream>
 #include <thread>
 
+#include "rs_env.hpp"
 #include "rs_internal.hpp"
 
 namespace rs {
@@ -255,25 +256,19 @@ void emit_input(std::ostringstream &o, const std::vector<uint16_t> &rows, std::v
 //   RS_AMD_NET_SHARED    0: the classic form instead of the shared-input form
 //   RS_AMD_NET_BALANCE   0: one wave per 8-output tile in the shared form
 struct Tuning {
-  int prefetch = 0, waves = 0, nt = 3, barrier = -1, units = 1, tile = 8, shared = -1, balance = 1, vmask = 1;
+  int prefetch = 0, waves = 0, nt = 3, barrier = -1, units = 1, tile = 8, shared = -1, balance = 1;
 };
-
-int env_int(const char *name, int def) {
-  const char *e = std::getenv(name);
-  return e && *e ? std::atoi(e) : def;
-}
 
 Tuning tuning() {
   Tuning t;
-  t.tile = env_int("RS_AMD_NET_TILE", t.tile) >= 8 ? 8 : 4;
-  t.shared = env_int("RS_AMD_NET_SHARED", t.shared);
-  t.balance = env_int("RS_AMD_NET_BALANCE", t.balance) != 0;
-  t.vmask = env_int("RS_AMD_NET_VMASK", t.vmask) != 0;
+  t.tile = env::num(env::NET_TILE) >= 8 ? 8 : 4;
+  t.shared = env::num(env::NET_SHARED);
+  t.balance = env::on(env::NET_BALANCE);
   return t;
 }
 
 std::string tuning_key(const Tuning &t) {
-  return "t" + std::to_string(t.tile) + "s" + std::to_string(t.shared) + (t.balance ? "" : "nb") + (t.vmask ? "" : "nv");
+  return "t" + std::to_string(t.tile) + "s" + std::to_string(t.shared) + (t.balance ? "" : "nb");
 }
 
 // Shared-input form (generate_shared): one workgroup of n_tiles waves per 4 KiB unit,
@@ -304,8 +299,9 @@ uint32_t kernel_tiles(const Tuning &t, const NetSpec &spec) {
 
 }  // namespace
 
-bool net_vmask() { return env_int("RS_AMD_NET_VMASK", 1) != 0; }
-std::string net_prelude() { return std::string("#define RS_VMASK ") + (net_vmask() ? "1\n" : "0\n") + kPrelude; }
+// RS_VMASK: only 1 is generated (the masks in SGPRs measured the same; the prelude keeps its
+// text so that code-object caches stay valid)
+std::string net_prelude() { return std::string("#define RS_VMASK 1\n") + kPrelude; }
 void emit_network_input(std::ostringstream &o, const std::vector<uint16_t> &rows, std::vector<bool> &init, int t) {
   emit_input(o, rows, init, t);
 }
@@ -319,7 +315,7 @@ bool supports(uint32_t n_in, uint32_t n_out, uint64_t shard_bytes) {
 
 // RS_AMD_NET_SMALL=0 keeps 1 / 2 KiB shards on the table kernels
 bool shard_ok(uint64_t shard_bytes) {
-  if (shard_bytes == 1024 || shard_bytes == 2048) return env_int("RS_AMD_NET_SMALL", 1) != 0;
+  if (shard_bytes == 1024 || shard_bytes == 2048) return env::on(env::NET_SMALL);
   return shard_bytes > 0 && shard_bytes % kUnitBytes == 0 && shard_bytes < (1ull << 32);
 }
 
@@ -350,7 +346,7 @@ std::string generate_shared(const NetSpec &spec, const std::string &name, const 
   const uint32_t mult = 1;
   const uint32_t BW = T * mult, nb = (n_in + BW - 1) / BW;
   std::ostringstream o;
-  o << "#define RS_NT " << tu.nt << "\n#define RS_VMASK " << tu.vmask << "\n" << kPrelude;
+  o << "#define RS_NT " << tu.nt << "\n#define RS_VMASK 1\n" << kPrelude;
   o << "extern \"C\" __global__ __launch_bounds__(" << 64 * T << ") ";
   if (tu.waves) o << "__attribute__((amdgpu_waves_per_eu(" << tu.waves << ", 8))) ";
   o << "void " << name
@@ -445,7 +441,7 @@ std::string generate_with(const NetSpec &spec, const std::string &name, const Tu
   // evict early) cost 10-15 % there, so by default they are kept for 1-tile maps only
   const int nt = n_tiles == 1 ? tu.nt : (tu.nt & 2);
   const uint32_t P = spec.pieces;  // stripes per wave unit (1, or 2 / 4 for 2 / 1 KiB shards)
-  o << "#define RS_NT " << nt << "\n#define RS_VMASK " << tu.vmask << "\n" << kPrelude;
+  o << "#define RS_NT " << nt << "\n#define RS_VMASK 1\n" << kPrelude;
   if (P > 1) o << kPreludeSmall;
   o << "extern \"C\" __global__ __launch_bounds__(256) ";
   if (tu.waves) o << "__attribute__((amdgpu_waves_per_eu(" << tu.waves << ", 8))) ";
@@ -585,12 +581,7 @@ std::string kernel_name(const NetSpec &spec, const std::string &key) {
 // of (hipRTC version, options, source) and its source length, so a process restart,
 // another rank or another thread finds the code object instead of recompiling.
 std::string cache_dir() {
-  if (const char *d = std::getenv("RS_AMD_CACHE_DIR")) return d;
-  if (const char *x = std::getenv("XDG_CACHE_HOME"))
-    if (*x) return std::string(x) + "/rs_amd";
-  if (const char *h = std::getenv("HOME"))
-    if (*h) return std::string(h) + "/.cache/rs_amd";
-  return "";
+  return env::given(env::CACHE_DIR) ? env::text(env::CACHE_DIR) : env::user_cache_dir();
 }
 
 std::atomic<uint64_t> g_compiles{0}, g_disk_hits{0};
@@ -675,7 +666,7 @@ bool compile(const std::string &src, std::vector<char> &code, std::string &err, 
   if (!path.empty() && !no_cache_read && cache_read(path, code)) {
     if (cached) *cached = path;
     g_disk_hits++;
-    if (std::getenv("RS_AMD_JIT_VERBOSE")) std::fprintf(stderr, "[rs_amd jit] code-object cache hit %s\n", path.c_str());
+    if (env::given(env::JIT_VERBOSE)) std::fprintf(stderr, "[rs_amd jit] code-object cache hit %s\n", path.c_str());
     return true;
   }
   hiprtcProgram prog;
@@ -705,30 +696,30 @@ bool compile(const std::string &src, std::vector<char> &code, std::string &err, 
 
 }  // namespace
 
+void dump_source(const std::string &name, const std::string &src) {
+  if (!env::given(env::JIT_DUMP)) return;
+  if (FILE *f = std::fopen((std::string(env::text(env::JIT_DUMP)) + "/" + name + ".hip").c_str(), "w")) {
+    std::fputs(src.c_str(), f);
+    std::fclose(f);
+  }
+}
+
 bool compile_check(const NetSpec &spec, std::string &err, double *ms, size_t *code_bytes) {
   const auto t0 = std::chrono::steady_clock::now();
   std::vector<char> code;
   const Tuning tu = tuning();
   NetSpec sp = spec;  // RS_AMD_NET_CHECK_PIECES: check the 2 / 4-stripe small-shard variant
-  const int cp = env_int("RS_AMD_NET_CHECK_PIECES", 1);  // 1, 2 or 4 (the layouts net_pieces() produces)
+  const int cp = env::num(env::NET_CHECK_PIECES);  // 1, 2 or 4 (the layouts net_pieces() produces)
   sp.pieces = static_cast<uint32_t>(cp == 2 || cp == 4 ? cp : 1);
   const std::string name = kernel_name(sp, spec_key(sp, -1, tu)), src = generate_with(sp, name, tu);
-  if (const char *dir = std::getenv("RS_AMD_JIT_DUMP")) {  // debug aid: keep the generated source
-    if (FILE *f = std::fopen((std::string(dir) + "/" + name + ".hip").c_str(), "w")) {
-      std::fputs(src.c_str(), f);
-      std::fclose(f);
-    }
-  }
+  dump_source(name, src);
   const bool ok = compile(src, code, err);
   if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (code_bytes) *code_bytes = code.size();
   return ok;
 }
 
-bool enabled() {
-  const char *e = std::getenv("RS_AMD_JIT");
-  return !(e && std::strcmp(e, "0") == 0);
-}
+bool enabled() { return env::on(env::JIT); }
 
 namespace {
 
@@ -764,7 +755,7 @@ std::unique_ptr<Kernel> build_source(const std::string &name, const std::string 
   }
   k->name = name;
   k->compile_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (std::getenv("RS_AMD_JIT_VERBOSE"))
+  if (env::given(env::JIT_VERBOSE))
     std::fprintf(stderr, "[rs_amd jit] %s compiled in %.0f ms (%zu B source, %zu B code)\n", name.c_str(),
                  k->compile_ms, src.size(), code.size());
   return k;
@@ -785,10 +776,7 @@ std::unique_ptr<Kernel> build(const NetSpec &spec, const std::string &key, const
 
 // Loaded modules are never unloaded (a launch may still use one); past
 // RS_AMD_JIT_CACHE_MAX of them (default 1024) new maps run on their table kernels.
-size_t module_cap() {
-  const char *e = std::getenv("RS_AMD_JIT_CACHE_MAX");
-  return e && *e ? static_cast<size_t>(std::max(0, std::atoi(e))) : 1024u;
-}
+size_t module_cap() { return static_cast<size_t>(env::num(env::JIT_CACHE_MAX)); }
 const char *kCapErr = "module cache full (RS_AMD_JIT_CACHE_MAX)";
 
 const Kernel *insert(const std::string &key, std::unique_ptr<Kernel> k) {  // g_mu held
@@ -891,11 +879,6 @@ void Worker::stop_at_exit() {
   g_worker.shutdown();
 }
 
-bool env_on(const char *name) {
-  const char *e = std::getenv(name);
-  return e && *e && std::strcmp(e, "0") != 0;
-}
-
 }  // namespace
 
 bool run_host_job(const std::string &key, std::function<void()> fn) {
@@ -915,8 +898,8 @@ bool run_host_job(const std::string &key, std::function<void()> fn) {
 }
 
 uint64_t max_async_blocks() {
-  const int v = env_int("RS_AMD_NET_ASYNC_BLOCKS", -1);
-  return v >= 0 ? static_cast<uint64_t>(v) : kMaxAsyncBlocks;
+  const int v = env::num(env::NET_ASYNC_BLOCKS);
+  return v != env::kAuto ? static_cast<uint64_t>(v) : kMaxAsyncBlocks;
 }
 
 bool supports_async(uint32_t n_in, uint32_t n_out, uint64_t shard_bytes) {
@@ -950,7 +933,7 @@ const Kernel *get(const NetSpec &spec, std::string &err) {
 
 const Kernel *get_async(const NetSpec &spec, std::string &err, bool &pending) {
   pending = false;
-  if (env_on("RS_AMD_JIT_SYNC")) return get(spec, err);
+  if (env::on(env::JIT_SYNC)) return get(spec, err);
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) {
     err = "hipGetDevice failed";
@@ -1016,7 +999,7 @@ const Kernel *get_source(const std::string &key, const std::string &name, const 
       err = kCapErr;
       return nullptr;
     }
-    if (async && !env_on("RS_AMD_JIT_SYNC")) {
+    if (async && !env::on(env::JIT_SYNC)) {
       pending = true;
       if (g_pending.count(full)) return nullptr;
       g_pending.insert(full);

@@ -64,6 +64,9 @@ uint32_t net_pieces(uint64_t shard_bytes);  // NetSpec::pieces for this shard si
 bool enabled();  // RS_AMD_JIT != 0 and hipRTC usable
 bool supports(uint32_t n_in, uint32_t n_out, uint64_t shard_bytes);
 
+// RS_AMD_JIT_DUMP: keep a compile-checked kernel's generated source as <dir>/<name>.hip
+void dump_source(const std::string &name, const std::string &src);
+
 // CUDA-style source of the kernel `name` (exposed for tests / inspection).
 std::string generate(const NetSpec &spec, const std::string &name);
 
@@ -71,8 +74,7 @@ std::string generate(const NetSpec &spec, const std::string &name);
 // st over a wave's 4 KiB unit; RS_NT must be defined first), and one input's
 // Four-Russians XOR network into accumulators a<r> (rows[r] = 16-bit mask of the
 // input planes feeding accumulator r; `init`: accumulators already assigned).
-std::string net_prelude();  // RS_AMD_NET_VMASK (default 1): transpose masks in VGPRs
-bool net_vmask();
+std::string net_prelude();
 void emit_network_input(std::ostringstream &o, const std::vector<uint16_t> &rows, std::vector<bool> &init, int t);
 
 struct Kernel {

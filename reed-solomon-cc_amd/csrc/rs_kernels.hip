@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "rs_device.hpp"
+#include "rs_env.hpp"
 #include "rs_internal.hpp"
 #include "rs_xform.hpp"
 
@@ -2121,9 +2122,7 @@ static int fit_nv(int nv, uint64_t shard_bytes) {
 }
 
 static int env_nv(int dflt) {
-  const char *e = getenv("RS_AMD_NV");
-  if (!e) return dflt;
-  const int v = atoi(e);
+  const int v = rs::env::num(rs::env::NV);
   return (v == 1 || v == 2 || v == 4) ? v : dflt;
 }
 
@@ -2210,10 +2209,8 @@ hipError_t launch_encode_low(const KernelChoice &kc, const EncodeArgs &a, hipStr
   // phase launches for every generic low-rate encode since the phase kernels stopped spilling
   // (round 5: RS(300,1000) 1 MiB x 16 33.1 -> 23.4 ms, 64 KiB x 8 1.25 -> 0.76 ms, RS(1000,4000)
   // 4 KiB x 64 2.74 -> 1.47 ms; profiles/r05/lowrate/encph.log). Round 4 kept the per-lane column
-  // walk where it had enough waves (then 32.7 vs 41.7 ms at 1 MiB x 16).
-  const char *ph = std::getenv("RS_AMD_LOW_ENC_PHASES");  // 1 / 0: force the phase launches / the walk
-  const bool phases = ph && *ph ? std::strcmp(ph, "1") == 0 : true;
-  if (kc.variant == Variant::kGeneric && a.chunk >= 64 && phases) return launch_encode_low_phases(a, s);
+  // walk where it had enough waves (then 32.7 vs 41.7 ms at 1 MiB x 16); it stays for chunk < 64.
+  if (kc.variant == Variant::kGeneric && a.chunk >= 64) return launch_encode_low_phases(a, s);
   if (kc.variant == Variant::kGeneric) {
     // a.scratch: `regions` C-position regions per stripe (low_encode): the coefficients, then
     // one per recovery chunk of a launch; the chunks run in groups of regions - 1

@@ -178,8 +178,7 @@ int get_low_encode_plan(int dev, uint64_t k, uint64_t m, uint64_t sb, std::share
 // the block form: C-point transforms only (C >= 128: launch_low_blocks' phase shapes), any
 // number of blocks up to kLowBlockMaxBlocks; RS_AMD_LOW_BLOCK=0 keeps the W-point decode
 bool block_ok(uint64_t k, uint64_t m, uint64_t sb) {
-  const char *ev = std::getenv("RS_AMD_LOW_BLOCK");
-  if (ev && std::strcmp(ev, "0") == 0) return false;
+  if (!env::on(env::LOW_BLOCK)) return false;
   const uint64_t C = ceil_pow2(k), W = ceil_pow2(C + m);
   return C >= 128 && W / C <= kLowBlockMaxBlocks && sb % 64 == 0;
 }
@@ -190,8 +189,7 @@ bool block_ok(uint64_t k, uint64_t m, uint64_t sb) {
 // (launch_low_blocks skips the others), at most ceil(m / C) < W / C of them, so it stays
 // below the W-point decode's transforms for every pattern.
 bool block_form(uint64_t k, uint64_t m, uint64_t sb, uint64_t e) {
-  const char *te = std::getenv("RS_AMD_LOW_TRIM");
-  return !(te && std::strcmp(te, "0") == 0) && e > 0 && block_ok(k, m, sb);
+  return env::on(env::LOW_TRIM) && e > 0 && block_ok(k, m, sb);
 }
 
 uint16_t log_of(uint16_t x) { return tables().log[x]; }
@@ -282,8 +280,7 @@ int get_low_decode_plan(int dev, uint64_t k, uint64_t m, uint64_t sb, const uint
   uint64_t e = 0;
   for (uint64_t i = 0; i < k; i++) e += present[i] ? 0 : 1;
   const bool net = map_net_ok(k, e, sb);
-  const char *te = std::getenv("RS_AMD_LOW_TRIM");
-  const bool trim = !(te && std::strcmp(te, "0") == 0);
+  const bool trim = env::on(env::LOW_TRIM);
   const bool blk = block_form(k, m, sb, e);
   std::string key = std::to_string(dev) + "/" + std::to_string(k) + "/" + std::to_string(m) + "/" +
                     std::to_string(net) + "/" + std::to_string(jit::max_blocks()) + "/" + (trim ? "t/" : "a/") +

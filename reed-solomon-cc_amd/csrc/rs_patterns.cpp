@@ -60,31 +60,19 @@ void wps_slot(int dev, uint64_t k, uint64_t m, uint32_t flags, std::shared_ptr<W
 }
 
 int fdec_mode() {
-  const char *e = std::getenv("RS_AMD_FDEC");
-  if (e && std::strcmp(e, "0") == 0) return 0;
-  if (e && std::strcmp(e, "1") == 0) return 1;
-  return 2;
+  const std::string e = env::text(env::FDEC);
+  return e == "0" ? 0 : e == "1" ? 1 : 2;
 }
 
-bool pdec_enabled() {
-  const char *e = std::getenv("RS_AMD_PDEC");
-  return fdec_mode() != 1 && !(e && std::strcmp(e, "0") == 0);
-}
+bool pdec_enabled() { return fdec_mode() != 1 && env::on(env::PDEC); }
 
-namespace {
-int env_num(const char *name, int def, int lo) {
-  const char *e = std::getenv(name);
-  return e && *e ? std::max(lo, std::atoi(e)) : def;
-}
-}  // namespace
-
-uint32_t pdec_after() { return static_cast<uint32_t>(env_num("RS_AMD_PDEC_AFTER", 2, 1)); }
-size_t pdec_queue() { return static_cast<size_t>(env_num("RS_AMD_PDEC_QUEUE", 2, 0)); }
+uint32_t pdec_after() { return static_cast<uint32_t>(env::num(env::PDEC_AFTER)); }
+size_t pdec_queue() { return static_cast<size_t>(env::num(env::PDEC_QUEUE)); }
 
 bool pdec_admit(int dev, uint64_t k, uint64_t m, const std::string &key) {
   static std::mutex mu;
   static std::map<std::string, std::set<std::string>> admitted;  // code -> pattern keys
-  const size_t cap = static_cast<size_t>(env_num("RS_AMD_PDEC_MAX", 32, 0));
+  const size_t cap = static_cast<size_t>(env::num(env::PDEC_MAX));
   const std::string code = std::to_string(dev) + "/" + std::to_string(k) + "/" + std::to_string(m);
   std::lock_guard<std::mutex> lk(mu);
   std::set<std::string> &s = admitted[code];
@@ -204,11 +192,16 @@ bool d2_drops_chunk(uint64_t k, uint64_t m, uint32_t flags) {
   return (flags & RS_FLAG_QUIRK_D2) && k > C && k % C == 0;
 }
 
+// RS_AMD_PATTERNS: "", "auto" and "psyn" leave the choice to the shape; "fft" keeps the FFT kernels
+bool patterns_auto() {
+  const std::string mode = env::text(env::PATTERNS);
+  return mode.empty() || mode == "auto" || mode == "psyn";
+}
+bool patterns_fft() { return std::string(env::text(env::PATTERNS)) == "fft"; }
+
 bool wps_enabled(uint64_t k, uint64_t m, uint64_t sb, uint32_t flags, uint32_t max_e) {
-  const char *pm = std::getenv("RS_AMD_PATTERNS");
-  const std::string mode = pm ? pm : "";
   return !(flags & RS_FLAG_QUIRK_D1) && !d2_drops_chunk(k, m, flags) &&
-         (mode.empty() || mode == "auto" || mode == "psyn") && fft_enabled() && fftnet::supports(k, m, sb, true) &&
+         patterns_auto() && fft_enabled() && fftnet::supports(k, m, sb, true) &&
          fftnet::pieces(sb) == 1 && sb % jit::kUnitBytes == 0 &&
          m <= 64;  // max_e up to m: output groups of 8 (rs_psyn.hpp launch_solve)
 }
@@ -221,17 +214,13 @@ bool wps_enabled(uint64_t k, uint64_t m, uint64_t sb, uint32_t flags, uint32_t m
 // 3.0 / 3.6 vs 2.2 / 4.0 ms; RS(100,20) max_e 20: 3.2 vs 3.3 ms. So auto takes it for
 // max_e >= 0.6 m (and where the solve has no 4 KiB units to run on); RS_AMD_FDEC=1 always.
 bool fdec_patterns_enabled(uint64_t k, uint64_t m, uint64_t sb, uint32_t flags, uint32_t max_e) {
-  const char *pm = std::getenv("RS_AMD_PATTERNS");
-  const std::string mode = pm ? pm : "";
-  if (!(mode.empty() || mode == "auto" || mode == "psyn") || m > 64 || !fdec_supports(k, m, sb, flags)) return false;
+  if (!patterns_auto() || m > 64 || !fdec_supports(k, m, sb, flags)) return false;
   return fdec_mode() == 1 || 5ull * max_e >= 3ull * m || sb % jit::kUnitBytes != 0;
 }
 
 bool psyn_enabled(uint64_t k, uint64_t m, uint64_t sb, uint32_t flags) {
-  const char *pm = std::getenv("RS_AMD_PATTERNS");
-  const std::string mode = pm ? pm : "";
   return !(flags & RS_FLAG_QUIRK_D1) && !d2_drops_chunk(k, m, flags) &&
-         (mode.empty() || mode == "auto" || mode == "psyn") && jit::enabled() && psyn::supports(k, m, sb);
+         patterns_auto() && jit::enabled() && psyn::supports(k, m, sb);
 }
 
 }  // namespace
@@ -256,10 +245,9 @@ const char *rs_patterns_kernel_name(uint64_t k, uint64_t m, size_t sb, uint32_t 
   } else if (wps_enabled(k, m, sb, flags, max_e)) {
     name = "fft_syndromes+psyn_solve";
   } else {
-    const char *pm = std::getenv("RS_AMD_PATTERNS");
     const uint64_t W = ceil_pow2(ceil_pow2(m) + k);
     const bool matrix =
-        !literal_decode(k, m, flags) && W <= 32 && max_e <= kMatrixMaxOut && !(pm && std::string(pm) == "fft");
+        !literal_decode(k, m, flags) && W <= 32 && max_e <= kMatrixMaxOut && !patterns_fft();
     name = matrix ? "pattern_matrix" : "pattern_fft";
   }
   return name.c_str();
@@ -434,9 +422,8 @@ int rs_reconstruct_batch_dev_patterns(uint64_t k, uint64_t m, size_t sb, uint64_
     if ((st = twiddle_plan(dev, W, flags, tw, off_fft))) return st;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // matrix path (below): corrected multiply, W <= 32, max_e <= 8
-    const char *pm = std::getenv("RS_AMD_PATTERNS");
     const bool use_matrix = !low && !literal_decode(k, m, flags) && W <= 32 && max_e <= kMatrixMaxOut &&
-                            !(pm && std::string(pm) == "fft");
+                            !patterns_fft();
     // per-stripe plan: logs u16 | pre RsTab | post RsTab | src i32 | dst i32 (W entries each)
     //                  [| trimmed present rows, matrix path]
     const uint64_t per = W * (2 + 2 * sizeof(RsTab) + 8);

@@ -536,8 +536,7 @@ int rs_psyn_compile_check(uint64_t k, uint64_t m, uint32_t flags, double *compil
 
 // RS_AMD_FFT_CHECK_INVERSE=1: the checks below take the inverse form (k == m == chunk)
 static bool check_inverse(uint64_t k, uint64_t m) {
-  const char *e = std::getenv("RS_AMD_FFT_CHECK_INVERSE");
-  return e && std::strcmp(e, "1") == 0 && fftnet::supports_inverse(k, m, fftnet::kUnitBytes);
+  return env::on(env::FFT_CHECK_INVERSE) && fftnet::supports_inverse(k, m, fftnet::kUnitBytes);
 }
 
 int rs_fft_compile_check(uint64_t k, uint64_t m, uint32_t flags, double *compile_ms, uint64_t *code_bytes,
@@ -551,7 +550,7 @@ int rs_fft_compile_check(uint64_t k, uint64_t m, uint32_t flags, double *compile
     spec.m = static_cast<uint32_t>(m);
     spec.flags = flags;
     // RS_AMD_FFT_CHECK_PIECES=2: the 1 KiB-shard variant (units of two stripes)
-    if (const char *pc = std::getenv("RS_AMD_FFT_CHECK_PIECES")) spec.pieces = std::strcmp(pc, "2") == 0 ? 2 : 1;
+    spec.pieces = static_cast<uint32_t>(env::num(env::FFT_CHECK_PIECES));
     spec.inverse = check_inverse(k, m);
     if (valu_ops) {
       const fftnet::Stats s = fftnet::stats(spec);

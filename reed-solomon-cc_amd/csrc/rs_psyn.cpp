@@ -29,7 +29,7 @@ bool skip_erased() { return true; }
 
 std::string key_of(const Spec &s) {
   std::string k = "psyn2:p" + std::to_string(prefetch()) + "w" + std::to_string(waves()) + "s" +
-                  std::to_string(skip_erased()) + "v" + std::to_string(jit::net_vmask()) + ":" + std::to_string(s.k) +
+                  std::to_string(skip_erased()) + "v1:" + std::to_string(s.k) +
                   ":" + std::to_string(s.m) + ":" + std::to_string(s.flags) + ":";
   k.append(reinterpret_cast<const char *>(s.images.data()), s.images.size() * sizeof(uint16_t));
   k.append(reinterpret_cast<const char *>(s.cantor.data()), s.cantor.size() * sizeof(uint16_t));
@@ -331,7 +331,7 @@ std::string generate_solve(const uint16_t *cantor, const std::string &name) {
 
 const jit::Kernel *get_solve(const uint16_t *cantor, std::string &err) {
   // v3: output groups (blockIdx.z), one alpha chain per syndrome
-  std::string key = "psolve:v3:o" + std::to_string(kSolveMaxOut) + "v" + std::to_string(jit::net_vmask()) + ":";
+  std::string key = "psolve:v3:o" + std::to_string(kSolveMaxOut) + "v1:";
   key.append(reinterpret_cast<const char *>(cantor), 16 * sizeof(uint16_t));
   uint64_t h = 1469598103934665603ull;
   for (unsigned char c : key) h = (h ^ c) * 1099511628211ull;
@@ -345,12 +345,7 @@ const jit::Kernel *get_solve(const uint16_t *cantor, std::string &err) {
 
 bool compile_check_solve(const uint16_t *cantor, std::string &err, double *ms, size_t *code_bytes) {
   const std::string src = generate_solve(cantor, "rs_psyn_solve_check");
-  if (const char *dir = std::getenv("RS_AMD_JIT_DUMP")) {
-    if (FILE *f = std::fopen((std::string(dir) + "/rs_psyn_solve_check.hip").c_str(), "w")) {
-      std::fputs(src.c_str(), f);
-      std::fclose(f);
-    }
-  }
+  jit::dump_source("rs_psyn_solve_check", src);
   return jit::compile_source_check(src, err, ms, code_bytes);
 }
 
@@ -388,12 +383,7 @@ const jit::Kernel *get(const Spec &s, std::string &err, bool &pending) {
 bool compile_check(const Spec &s, std::string &err, double *ms, size_t *code_bytes) {
   const std::string name = name_of(s);
   const std::string src = generate(s, name);
-  if (const char *dir = std::getenv("RS_AMD_JIT_DUMP")) {
-    if (FILE *f = std::fopen((std::string(dir) + "/" + name + ".hip").c_str(), "w")) {
-      std::fputs(src.c_str(), f);
-      std::fclose(f);
-    }
-  }
+  jit::dump_source(name, src);
   return jit::compile_source_check(src, err, ms, code_bytes);
 }
 

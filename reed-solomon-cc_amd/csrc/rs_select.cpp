@@ -15,16 +15,14 @@ namespace host {
 // table register kernel — RS(40,12) 1 MiB 4.08 -> 2.95 ms, RS(100,6) 2.85 -> 2.35 ms,
 // RS(100,4) 2.49 -> 2.30 ms, RS(200,8) 2.75 -> 2.58 ms (profiles/r02/sweep_encode_async_net.jsonl).
 bool encode_net_async(uint64_t k, uint64_t m) {
-  const char *sh = std::getenv("RS_AMD_NET_SHARED");
-  if (sh && *sh && std::strcmp(sh, "0") == 0) return false;
+  if (env::num(env::NET_SHARED) == 0) return false;
   return m <= jit::kMaxOut && !fftnet::supports(k, m, fftnet::kUnitBytes) &&
          jit::supports_async(static_cast<uint32_t>(k), static_cast<uint32_t>(m), jit::kUnitBytes);
 }
 
 bool encode_net_ok(uint64_t sb) {
   if (jit::net_pieces(sb) == 1) return true;
-  const char *e = std::getenv("RS_AMD_NET_SMALL_ENCODE");
-  return e && *e && std::strcmp(e, "0") != 0;
+  return env::on(env::NET_SMALL_ENCODE);
 }
 
 // Multiplies the FFT reconstruct performs for a pattern (plan-time estimate used to
@@ -50,10 +48,7 @@ uint64_t fft_decode_mul_count(uint64_t k, uint64_t m, uint64_t present_count, ui
   return n;
 }
 
-const char *decode_mode_env() {
-  const char *e = std::getenv("RS_AMD_DECODE");
-  return e ? e : "auto";
-}
+const char *decode_mode_env() { return env::given(env::DECODE) ? env::text(env::DECODE) : "auto"; }
 
 
 // Reconstruct kernel family for a pattern: 0 = FFT kernels (root.zig:268-335 as

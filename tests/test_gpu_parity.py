@@ -352,17 +352,14 @@ def test_repeatable_and_nan_free_of_state():
     assert (gpu_encode(k, m, d) == gpu_encode(k, m, d)).all()
 
 
-@pytest.mark.parametrize("pinned,gap,slice_mb,stage", [(True, None, None, None), (False, None, None, None),
-                                                       (True, "1", None, None), (True, "64", None, None),
-                                                       (False, None, "1", None), (False, "1", "2", None),
-                                                       (False, None, "1", "0")])
-def test_host_batch_pipeline(oracle, monkeypatch, pinned, gap, slice_mb, stage):
-    """rs_encode_batch_host / rs_reconstruct_batch_host (H2D -> kernel -> D2H ring) == oracle;
-    gap: RS_AMD_HOST_GAP, missing rows bridged inside one copy of present rows (their bytes
-    cross PCIe and are never read), here with missing data and recovery rows. Pageable
+@pytest.mark.parametrize("pinned,slice_mb,stage", [(True, None, None), (False, None, None), (False, "1", None),
+                                                   (False, "2", None), (False, "1", "0")])
+def test_host_batch_pipeline(oracle, monkeypatch, pinned, slice_mb, stage):
+    """rs_encode_batch_host / rs_reconstruct_batch_host (H2D -> kernel -> D2H ring) == oracle,
+    here with missing data and recovery rows (one copy per run of present rows). Pageable
     buffers go through the ring's pinned staging (RS_AMD_HOST_STAGE=0: the runtime's path),
     over many slices (RS_AMD_HOST_SLICE_MB) so both slots' staging is reused."""
-    for name, val in (("RS_AMD_HOST_GAP", gap), ("RS_AMD_HOST_SLICE_MB", slice_mb), ("RS_AMD_HOST_STAGE", stage)):
+    for name, val in (("RS_AMD_HOST_SLICE_MB", slice_mb), ("RS_AMD_HOST_STAGE", stage)):
         if val is not None:
             monkeypatch.setenv(name, val)
     k, m, sb, n = 10, 4, 1 << 16, 37  # several pipeline slices at 256 MiB / (k*sb) = 409 stripes? -> force small
