@@ -2,8 +2,8 @@
 // error reporting, plan caches, kernel selection, plans, and the entry points the
 // C ABI files (rs_batch_dev.cpp, rs_patterns.cpp, rs_lowrate.cpp, rs_host_batch.cpp,
 // rs_oneshot.cpp) share. Host-side mirror of root.zig's checks and error
-// precedence; every device computation runs in rs_kernels.hip or in a hipRTC
-// kernel (rs_jit / rs_fftnet / rs_psyn); there is no CPU compute path.
+// precedence; every device computation runs in the precompiled kernels
+// (rs_kernels.hip, rs_phase_kernels.hip, rs_plan_kernels.hip) or in a hipRTC kernel (rs_jit / rs_fftnet / rs_psyn); there is no CPU compute path.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,5 +1,6 @@
 // rs_internal.hpp — launch interface between the host codec (rs_host.hpp and the files behind it) and
-// the HIP kernels (rs_kernels.hip). Not part of the public ABI.
+// the HIP kernels (rs_kernels.hip, rs_phase_kernels.hip, rs_plan_kernels.hip). Not part of the
+// public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -123,8 +124,9 @@ KernelChoice choose_decode_w(uint64_t W, uint64_t shard_bytes, int max_nv);  // 
 // recovery chunk j. Register kernel for C <= 32, else the scratch-walking generic kernel
 // (scratch [stripe][2C][sb]).
 KernelChoice choose_encode_low(uint64_t C, uint64_t shard_bytes, int max_nv);
-// the phases of the column transforms (rs_kernels.hip xform_ph): sub-problems of n positions at
-// distance 2^dlo_log, first table ti of the size's IFFT (inv) or FFT table list
+// the phases of the column transforms (rs_phase_kernels.hip xform_phases, as rs_kernels.hip
+// xform_ph groups them on the device): sub-problems of n positions at distance 2^dlo_log, first
+// table ti of the size's IFFT (inv) or FFT table list
 struct XPhase {
   uint32_t n, dlo_log;
   uint64_t ti;
@@ -132,6 +134,10 @@ struct XPhase {
 void xform_phases(uint64_t size, bool inv, std::vector<XPhase> &out);
 
 hipError_t launch_encode_low(const KernelChoice &kc, const EncodeArgs &a, hipStream_t s);
+// what launch_encode_low and launch_decode run for the generic variant, one launch per transform
+// phase (rs_phase_kernels.hip): the low-rate encode for chunk >= 64 and the reconstruct for any W
+hipError_t launch_encode_low_phases(const EncodeArgs &a, hipStream_t s);
+hipError_t launch_decode_generic(const DecodeArgs &a, hipStream_t s);
 
 // Low-rate reconstruct in block form (rs_lowrate.cpp, C = ceilPow2(k) >= 128): C-point
 // transforms only. enc: originals (erased ones flagged in enc.skip), tabs = the low-rate
@@ -194,7 +200,7 @@ hipError_t launch_psyn_plan(const uint8_t *present, uint64_t present_stride, uin
                             uint32_t *plan, uint32_t plan_dw, int32_t *status, hipStream_t s);
 
 // Per-stripe plan of the wide-code path: FFT mask block (dmw words) + solve header
-// (rs_kernels.hip k_wps_plan / k_wps_plan_wave); plan_dw >= dmw + 2 + 64 + 64 * cs,
+// (rs_plan_kernels.hip k_wps_plan / k_wps_plan_wave); plan_dw >= dmw + 2 + 64 + 64 * cs,
 // cs = wps_coef_stride(max_e) (coefficients per syndrome: 8, or max_e rounded up to 8), m <= 64
 uint32_t wps_coef_stride(uint32_t max_e);
 hipError_t launch_wps_plan(const uint8_t *present, uint64_t present_stride, uint32_t k, uint32_t m, uint32_t max_e,

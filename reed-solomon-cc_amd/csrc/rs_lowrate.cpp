@@ -9,7 +9,8 @@
 //  * encode (rs_gf.hpp scalar_encode_low): originals at positions [0, k) of one chunk
 //    C = ceilPow2(k), coefficients = IFFT(C, trunc k, skew 0), recovery chunk j =
 //    FFT(coefficients, trunc min(C, m - jC), skew (j + 1) C). FFT-form kernels
-//    (rs_kernels.hip k_encode_low_reg for C <= 32, k_encode_low_generic otherwise).
+//    (rs_kernels.hip k_encode_low_reg for C <= 32; rs_phase_kernels.hip
+//    launch_encode_low_phases for C >= 64).
 //  * reconstruct (rs_gf.hpp scalar_reconstruct_low): the erasure-locator decode of
 //    root.zig:268-335 in the low-rate position layout (recovery at [C, C + m), [C + m, W)
 //    erased), on the decode kernels with the FFT truncated to k (k_decode_reg for

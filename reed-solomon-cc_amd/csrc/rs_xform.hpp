@@ -1,14 +1,15 @@
 // rs_xform.hpp — the column transforms' device primitives shared by the precompiled kernels
-// (rs_kernels.hip):
+// (rs_kernels.hip: the codec kernels and the column walk; rs_phase_kernels.hip: the phase kernels):
 // Generic.zig:15-147 on a register set of N positions (ifft_sub / fft_sub, wave-uniform
 // twiddle tables in SGPRs), the opaque-value helpers that keep table addresses from being
-// hoisted out of loops, and the buffer resources of shard rows.
+// hoisted out of loops, the buffer resources of shard rows, and the launch geometry.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "rs_device.hpp"
+#include "rs_internal.hpp"
 
 namespace rs {
 namespace dev {
@@ -129,4 +130,25 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t zero_rsrc() {
   return __builtin_amdgcn_make_buffer_rsrc(nullptr, static_cast<short>(0), 0, 0x00020000);
 }
 }  // namespace dev
+
+// ---- what the codec kernels and the phase kernels both need
+constexpr int kBlock = 256;  // lanes per workgroup
+
+// x = column units of one stripe (nv dword pairs per lane), y = stripes (at most 65535 a launch)
+inline dim3 grid_for(uint64_t shard_bytes, int nv, uint64_t n_stripes) {
+  const uint64_t units = shard_bytes / 64 * (8 / nv);
+  const uint64_t bx = (units + kBlock - 1) / kBlock;
+  const uint64_t by = n_stripes < 65535 ? n_stripes : 65535;
+  return dim3(static_cast<uint32_t>(bx), static_cast<uint32_t>(by ? by : 1), 1);
+}
+
+inline uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
+
+// Encode of a partial data set (reconstruct by syndromes, rs_batch_dev.cpp; the low-rate block
+// form, rs_lowrate.cpp): data shard `idx` flagged in the skip bitmask is read as zeros (never
+// touched).
+__device__ __forceinline__ bool skipped(const EncodeArgs &a, uint32_t idx) {
+  typedef const __attribute__((address_space(4))) uint32_t *CU;
+  return a.skip && ((((CU)(a.skip))[idx >> 5] >> (idx & 31)) & 1u);
+}
 }  // namespace rs

@@ -1,4 +1,4 @@
-"""Dataflow model of the generic reconstruct's launch sequence (rs_kernels.hip
+"""Dataflow model of the generic reconstruct's launch sequence (rs_phase_kernels.hip
 launch_decode_generic / k_dphase): the phase schedule (xform_phases), the sub-problem ->
 positions map, the IFFT's zero tail (positions past round_up(trunc, span) neither written
 nor read), the formal derivative split into in-register bits and partner loads, the FFT's
@@ -88,7 +88,7 @@ def decode_ref(src, W, trunc, trunc_fft, dst):
     return {p: x[p] for p in dst if p < trunc_fft}
 
 
-# ---- the launch sequence, as rs_kernels.hip writes it
+# ---- the launch sequence, as rs_phase_kernels.hip writes it
 def xform_phases(size, inv):
     lg = size.bit_length() - 1
     n4, layer, r2_done, out = lg // 2, 0, not (lg & 1), []
@@ -262,7 +262,7 @@ def test_phased_decode_matches_layer_walk(W, trunc, trunc_fft):
     assert decode_phased(src, W, trunc, trunc_fft, dst) == decode_ref(src, W, trunc, trunc_fft, dst)
 
 
-# ---- the low-rate encode's launch sequence (rs_kernels.hip launch_encode_low_phases)
+# ---- the low-rate encode's launch sequence (rs_phase_kernels.hip launch_encode_low_phases)
 def encode_ref(data, C, k, m):
     x = [data.get(p, 0) for p in range(C)]
     ifft_ref(x, C, k)

@@ -1,4 +1,4 @@
-"""Model of the low-rate block-form reconstruct's launch sequence (rs_kernels.hip
+"""Model of the low-rate block-form reconstruct's launch sequence (rs_phase_kernels.hip
 launch_low_blocks: k_ephase GATHER / FFT / SYN, k_lbfinal, k_dphase LSUM / SCATTER) with the
 field arithmetic of the library's own tables (R.table: exp / log / skew / log_walsh), one
 symbol per row, against the lost data.
@@ -224,7 +224,7 @@ def block_plan(k, m, present):  # build_block_plan
                 post=post, skip=[not present[i] for i in range(k)])
 
 
-# ---------------------------------------------------------------- device phases (rs_kernels.hip)
+# ---------------------------------------------------------------- device phases (rs_phase_kernels.hip)
 def xform_phases(size, inv):
     lg = size.bit_length() - 1
     n4, layer, r2_done, ti, out = lg // 2, 0, not (lg & 1), 0, []
