@@ -144,6 +144,30 @@ int rs_reconstruct_batch_dev_patterns(uint64_t original_count, uint64_t recovery
                                       uint64_t restored_stripe_stride, int32_t *d_status, uint32_t flags,
                                       rs_stream_t stream);
 
+/* Verify (scrub): for every stripe, compare each stored recovery shard with what
+ * rs_encode_batch_dev (same k, m, shard_bytes, flags) would write for the stripe's originals.
+ * Neither input is written. d_bad: device, n_stripes rows of m bytes (row stride bad_stride,
+ * 0 = m): d_bad[s][r] = 1 if recovery shard r of stripe s differs in any byte, else 0. Every
+ * one of the n*m flag bytes is written; bytes between rows are not touched. d_bad_count
+ * (device, optional): receives the number of flags set.
+ * Accepts everything the encode accepts (any even shard_bytes, 1 / 2 KiB shards, 4-byte
+ * aligned buffers, low-rate codes, the quirk flags), always meaning "what the encode would
+ * write", and validates in the encode's order (n_stripes == 0: RS_OK, nothing written; a NULL
+ * pointer, a stride below the row size or 0 < bad_stride < m: RS_ERR_INVALID_ARGUMENT).
+ * A set flag says that the stripe is inconsistent and which recovery rows disagree with the
+ * originals, not which shard is the corrupt one: one corrupt recovery shard sets one flag; one
+ * corrupt original sets all m flags under the corrected arithmetic (flags == 0), because every
+ * block of the encode is a multiplication by a nonzero field element.
+ * Slices of stripes are encoded into a scratch of at most RS_AMD_SCRATCH_CAP_MB (by the
+ * encode's own kernels) and compared with the stored shards: k + 3m rows of traffic per stripe,
+ * and no second parity buffer of the whole batch. */
+int rs_verify_batch_dev(uint64_t original_count, uint64_t recovery_count, size_t shard_bytes, uint64_t n_stripes,
+                        const void *d_original, uint64_t original_stripe_stride, const void *d_recovery,
+                        uint64_t recovery_stripe_stride, uint8_t *d_bad, uint64_t bad_stride, uint64_t *d_bad_count,
+                        uint32_t flags, rs_stream_t stream);
+/* The path a verify takes: "<rs_encode_kernel_name>+verify_compare". */
+const char *rs_verify_kernel_name(uint64_t original_count, uint64_t recovery_count, size_t shard_bytes);
+
 /* -------------------------------------- host-resident batches (end to end)
  * Same layouts and semantics as the *_dev calls, but the batch lives in HOST
  * memory: the library streams it through HBM in slices on a 2-slot

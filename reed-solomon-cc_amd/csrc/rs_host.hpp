@@ -1,7 +1,7 @@
 // rs_host.hpp — internal interface of the host codec (librs_amd.so): validation and
 // error reporting, plan caches, kernel selection, plans, and the entry points the
 // C ABI files (rs_batch_dev.cpp, rs_patterns.cpp, rs_lowrate.cpp, rs_host_batch.cpp,
-// rs_oneshot.cpp) share. Host-side mirror of root.zig's checks and error
+// rs_oneshot.cpp, rs_verify.cpp) share. Host-side mirror of root.zig's checks and error
 // precedence; every device computation runs in the precompiled kernels
 // (rs_kernels.hip, rs_phase_kernels.hip, rs_plan_kernels.hip) or in a hipRTC kernel (rs_jit / rs_fftnet / rs_psyn); there is no CPU compute path.
 #pragma once

@@ -229,6 +229,18 @@ hipError_t launch_trim_present(const uint8_t *present, uint64_t present_stride, 
 hipError_t launch_tail_pack(const uint8_t *src, uint64_t src_stripe_stride, uint8_t *dst, uint64_t dst_stripe_stride,
                             uint64_t sb, uint64_t n, bool unpack, hipStream_t s);
 
+// Verify (rs_verify.cpp): a [n][m][sb] (the encode of the originals, stripe stride
+// a_stripe_stride) against b (the stored recovery shards): flag [s][r] (bytes, row stride
+// bad_stride, zeroed by the caller) is set to 1 where shard r of stripe s differs in any byte.
+// 16-byte loads when both bases, both strides and sb allow them, dwords when all are 4-byte
+// aligned, bytes otherwise.
+hipError_t launch_verify_compare(const uint8_t *a, uint64_t a_stripe_stride, const uint8_t *b,
+                                 uint64_t b_stripe_stride, uint64_t sb, uint64_t n, uint32_t m, uint8_t *bad,
+                                 uint64_t bad_stride, hipStream_t s);
+// *count = the number of nonzero flags among [n][m] (row stride bad_stride); zeroes *count first
+hipError_t launch_verify_count(const uint8_t *bad, uint64_t bad_stride, uint64_t n, uint32_t m, uint64_t *count,
+                               hipStream_t s);
+
 // Engine shims (generic, in place on a single-stripe work buffer)
 hipError_t launch_engine_fft(uint8_t *work, uint64_t shard_bytes, uint64_t pos, uint64_t size, uint64_t trunc,
                              const RsTab *tabs, bool inverse, hipStream_t s);

@@ -17,6 +17,8 @@
 //    each lane walking its column (xform_ph). The generic reconstruct and the low-rate
 //    codes of 64 positions and more run as one launch per transform phase:
 //    rs_phase_kernels.hip.
+//  * k_verify_compare / k_verify_count: the compare of rs_verify_batch_dev (an encode into
+//    a scratch compared with the stored recovery shards) and the count of its flags.
 //  * k_engine_transform / k_mul_scalar: the Engine seam (Generic.zig) as test shims.
 // The per-stripe plan kernels are in rs_plan_kernels.hip.
 #include <hip/hip_runtime.h>
@@ -881,6 +883,62 @@ __global__ __launch_bounds__(256) void k_tail_pack(const uint8_t *__restrict__ s
   }
 }
 
+// ================================================================== verify
+// The compare of rs_verify_batch_dev: a = the encode of a slice's originals ([n][m][sb]),
+// b = the stored recovery shards. A workgroup takes kVerifySeg bytes of one shard (work items
+// flattened over stripe, shard, segment; grid-stride, 64-bit indices), ORs the XOR of the two
+// and, where a wave saw a difference, its lane 0 stores 1 to the shard's flag (zeroed by the
+// host; several waves may store the same 1). MODE 2: 16-byte loads, 1: dwords, 0: bytes
+// (tails make shard starts 2-byte aligned).
+constexpr uint32_t kVerifySeg = 16384;  // a multiple of 16: segment starts keep the shard's alignment
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_verify_compare(const uint8_t *__restrict__ a, uint64_t a_stride,
+                                                        const uint8_t *__restrict__ b, uint64_t b_stride,
+                                                        uint64_t sb, uint64_t n, uint32_t m, uint64_t segs,
+                                                        uint8_t *__restrict__ bad, uint64_t bad_stride) {
+  const uint64_t per_stripe = static_cast<uint64_t>(m) * segs, total = n * per_stripe;
+  for (uint64_t w = blockIdx.x; w < total; w += gridDim.x) {
+    const uint64_t s = w / per_stripe, rem = w % per_stripe;
+    const uint64_t r = rem / segs, base = (rem % segs) * kVerifySeg;
+    const uint32_t len = static_cast<uint32_t>(sb - base < kVerifySeg ? sb - base : kVerifySeg);
+    const uint8_t *pa = a + s * a_stride + r * sb + base;
+    const uint8_t *pb = b + s * b_stride + r * sb + base;
+    uint32_t d = 0;
+    if (MODE == 2) {
+      typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+      for (uint32_t i = threadIdx.x * 16u; i + 16u <= len; i += 256u * 16u) {
+        const v4u x = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(pa + i));
+        const v4u y = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(pb + i));
+        d |= (x[0] ^ y[0]) | (x[1] ^ y[1]) | (x[2] ^ y[2]) | (x[3] ^ y[3]);
+      }
+    } else if (MODE == 1) {
+      for (uint32_t i = threadIdx.x * 4u; i + 4u <= len; i += 256u * 4u)
+        d |= *reinterpret_cast<const uint32_t *>(pa + i) ^ *reinterpret_cast<const uint32_t *>(pb + i);
+    } else {
+      for (uint32_t i = threadIdx.x; i < len; i += 256u) d |= static_cast<uint32_t>(pa[i] ^ pb[i]);
+    }
+    if (__builtin_amdgcn_ballot_w64(d != 0u) != 0ull && (threadIdx.x & 63u) == 0u) bad[s * bad_stride + r] = 1;
+  }
+}
+
+// The number of nonzero flags among [n][m]: per-workgroup partial sums added to *count
+// (zeroed by the host on the stream).
+__global__ __launch_bounds__(256) void k_verify_count(const uint8_t *__restrict__ bad, uint64_t bad_stride, uint64_t n,
+                                                      uint32_t m, unsigned long long *count) {
+  __shared__ uint32_t part;
+  if (threadIdx.x == 0) part = 0;
+  __syncthreads();
+  const uint64_t total = n * m;
+  uint32_t c = 0;
+  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x; i < total;
+       i += static_cast<uint64_t>(gridDim.x) * 256u)
+    c += bad[i / m * bad_stride + i % m] != 0;
+  if (c) atomicAdd(&part, c);
+  __syncthreads();
+  if (threadIdx.x == 0 && part) atomicAdd(count, static_cast<unsigned long long>(part));
+}
+
 // ========================================================== engine test shims
 __global__ __launch_bounds__(kBlock) void k_engine_transform(uint8_t *work, uint64_t sb, uint64_t pos, uint64_t size,
                                                              uint64_t trunc, const RsTab *tabs, int inverse) {
@@ -1197,6 +1255,39 @@ hipError_t launch_tail_pack(const uint8_t *src, uint64_t src_stripe_stride, uint
   const uint64_t blocks = (n * 64 + 255) / 256;
   hipLaunchKernelGGL(k_tail_pack, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, s, src, src_stripe_stride, dst,
                      dst_stripe_stride, sb, n, unpack ? 1 : 0);
+  return hipGetLastError();
+}
+
+hipError_t launch_verify_compare(const uint8_t *a, uint64_t a_stripe_stride, const uint8_t *b,
+                                 uint64_t b_stripe_stride, uint64_t sb, uint64_t n, uint32_t m, uint8_t *bad,
+                                 uint64_t bad_stride, hipStream_t s) {
+  if (n == 0 || m == 0 || sb == 0) return hipSuccess;
+  trace_launch("k_verify_compare");
+  const uint64_t segs = (sb + kVerifySeg - 1) / kVerifySeg, total = n * m * segs;
+  // grid-stride over the work items: the grid stays inside the launch limits for any batch
+  const dim3 grid(static_cast<uint32_t>(std::min<uint64_t>(total, 1u << 20)));
+  const uint64_t al = reinterpret_cast<uint64_t>(a) | reinterpret_cast<uint64_t>(b) | a_stripe_stride |
+                      b_stripe_stride | sb;
+  if (al % 16 == 0)
+    hipLaunchKernelGGL(k_verify_compare<2>, grid, dim3(256), 0, s, a, a_stripe_stride, b, b_stripe_stride, sb, n, m,
+                       segs, bad, bad_stride);
+  else if (al % 4 == 0)
+    hipLaunchKernelGGL(k_verify_compare<1>, grid, dim3(256), 0, s, a, a_stripe_stride, b, b_stripe_stride, sb, n, m,
+                       segs, bad, bad_stride);
+  else
+    hipLaunchKernelGGL(k_verify_compare<0>, grid, dim3(256), 0, s, a, a_stripe_stride, b, b_stripe_stride, sb, n, m,
+                       segs, bad, bad_stride);
+  return hipGetLastError();
+}
+
+hipError_t launch_verify_count(const uint8_t *bad, uint64_t bad_stride, uint64_t n, uint32_t m, uint64_t *count,
+                               hipStream_t s) {
+  hipError_t e = hipMemsetAsync(count, 0, sizeof(uint64_t), s);
+  if (e != hipSuccess || n == 0 || m == 0) return e;
+  trace_launch("k_verify_count");
+  const uint64_t blocks = std::min<uint64_t>((n * m + 255) / 256, 1024);
+  hipLaunchKernelGGL(k_verify_count, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, s, bad, bad_stride, n, m,
+                     reinterpret_cast<unsigned long long *>(count));
   return hipGetLastError();
 }
 

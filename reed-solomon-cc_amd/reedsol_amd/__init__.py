@@ -7,7 +7,7 @@ after the Zig error set. Everything is computed by the gfx950 HIP kernels of
 ``librs_amd.so`` through its C ABI (include/reedsol.h); there is no CPU
 fallback — without the library or a gfx950 device every call raises.
 
-Device batch API (``encode_batch_dev`` / ``reconstruct_batch_dev``) takes
+Device batch API (``encode_batch_dev`` / ``reconstruct_batch_dev`` / ``verify_batch_dev``) takes
 torch tensors that already live in HBM (PyTorch is only the allocator and
 stream provider here).
 """
@@ -79,6 +79,8 @@ def lib():
         "rs_reconstruct_batch_dev": (C.c_int, [u64, u64, sz, u64, vp, vp, u64, vp, u64, vp, u64, u32, vp]),
         "rs_reconstruct_batch_dev_patterns": (C.c_int, [u64, u64, sz, u64, vp, u64, u32, vp, u64, vp, u64, vp, u64,
                                                         vp, u32, vp]),
+        "rs_verify_batch_dev": (C.c_int, [u64, u64, sz, u64, vp, u64, vp, u64, vp, u64, vp, u32, vp]),
+        "rs_verify_kernel_name": (C.c_char_p, [u64, u64, sz]),
         "rs_encode_batch_host": (C.c_int, [u64, u64, sz, u64, vp, u64, vp, u64, u32]),
         "rs_reconstruct_batch_host": (C.c_int, [u64, u64, sz, u64, vp, vp, u64, vp, u64, vp, u64, u32]),
         "rs_encode_batch_host_multi": (C.c_int, [u64, u64, sz, u64, vp, u64, vp, u64, u32, vp, C.c_int]),
@@ -273,6 +275,33 @@ def reconstruct_batch_dev(original_count: int, recovery_count: int, present: Seq
         original_count, recovery_count, sb, n, pres, C.c_void_p(original.data_ptr()), original.stride(0),
         C.c_void_p(recovery.data_ptr()), recovery.stride(0), C.c_void_p(restored.data_ptr()), restored.stride(0),
         flags, _stream_handle(stream)))
+
+
+def verify_batch_dev(original_count: int, recovery_count: int, data, parity, bad=None, count=None,
+                     flags: int = FLAG_CORRECTED, stream=None):
+    """Scrub: data [n, k, sb] and stored parity [n, m, sb] (uint8 CUDA tensors, last two
+    dimensions contiguous) -> bad, a torch.uint8 tensor [n, m] (allocated when None; its row
+    stride may exceed m): bad[s, r] = 1 where recovery shard r of stripe s is not what the
+    encode writes for the stripe's originals. count: optional int64 CUDA tensor of one
+    element, receives the number of flags set. Asynchronous on `stream`; returns bad."""
+    n, k, sb = data.shape
+    assert k == original_count and parity.shape == (n, recovery_count, sb)
+    assert data.is_cuda and parity.is_cuda
+    assert n == 0 or (data[0].is_contiguous() and parity[0].is_contiguous())
+    if bad is None:
+        import torch
+        bad = torch.empty((n, recovery_count), dtype=torch.uint8, device=data.device)
+    assert bad.is_cuda and bad.shape == (n, recovery_count) and (n == 0 or bad[0].is_contiguous())
+    _check(lib().rs_verify_batch_dev(
+        original_count, recovery_count, sb, n, C.c_void_p(data.data_ptr()), data.stride(0),
+        C.c_void_p(parity.data_ptr()), parity.stride(0), C.c_void_p(bad.data_ptr()), bad.stride(0),
+        C.c_void_p(count.data_ptr()) if count is not None else None, flags, _stream_handle(stream)))
+    return bad
+
+
+def verify_kernel_name(k, m, shard_bytes) -> str:
+    """Path of verify_batch_dev for these arguments (include/reedsol.h)."""
+    return lib().rs_verify_kernel_name(k, m, shard_bytes).decode()
 
 
 def encode_batch_host(original_count: int, recovery_count: int, data, parity, flags: int = FLAG_CORRECTED):
