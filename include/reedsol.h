@@ -120,8 +120,14 @@ int rs_encode_batch_dev(uint64_t original_count, uint64_t recovery_count, size_t
 
 /* Reconstruct the missing originals of every stripe; one erasure pattern for
  * the whole batch. present: host array of k+m flags (originals, then
- * recovery). Missing slots of d_original/d_recovery are never read.
- *   d_restored: [n_stripes][e][shard_bytes], e = missing originals, ascending index. */
+ * recovery). The slots of missing shards still lie inside the caller's rows of
+ * d_original / d_recovery (the layout does not change), but their contents never
+ * influence a result and they are never written: they may hold garbage, stale data or
+ * another object's shards. The same holds for every reconstruct entry point below (per-stripe
+ * patterns, host batches, rs_decode, the Decoder), and no input buffer is written at all
+ * (tests/test_gpu_missing_slots.py checks it for every kernel family).
+ *   d_restored: [n_stripes][e][shard_bytes], e = missing originals, ascending index.
+ * Nothing else of d_restored is written (stride padding, rows past the batch). */
 int rs_reconstruct_batch_dev(uint64_t original_count, uint64_t recovery_count, size_t shard_bytes,
                              uint64_t n_stripes, const uint8_t *present, const void *d_original,
                              uint64_t original_stripe_stride, const void *d_recovery,
@@ -135,8 +141,9 @@ int rs_reconstruct_batch_dev(uint64_t original_count, uint64_t recovery_count, s
  * 64K-point FWHTs. Stripe s restores its missing originals, ascending, into
  * slots [0, e_s) of its d_restored row ([n][max_e][shard_bytes]); slots >= e_s
  * are not written. d_status (device, n int32, may be NULL) receives per stripe
- * RS_OK, RS_ERR_NOT_ENOUGH_SHARDS (< k present) or RS_ERR_INVALID_ARGUMENT
- * (e_s > max_e: restored slots past max_e are dropped). */
+ * RS_OK, RS_ERR_NOT_ENOUGH_SHARDS (< k present: no slot of the stripe's row is written)
+ * or RS_ERR_INVALID_ARGUMENT (e_s > max_e: restored slots past max_e are dropped). Bytes
+ * of a d_present row past its k+m flags are ignored. */
 int rs_reconstruct_batch_dev_patterns(uint64_t original_count, uint64_t recovery_count, size_t shard_bytes,
                                       uint64_t n_stripes, const uint8_t *d_present, uint64_t present_stride,
                                       uint32_t max_e, const void *d_original, uint64_t original_stripe_stride,

@@ -165,7 +165,9 @@ int rs_decode(uint64_t k, uint64_t m, size_t sb, const uint8_t *const *original,
       int dev;
       if ((st = current_device(&dev))) return st;
       // staging: [originals k][recovery m][restored e], each region 256-B aligned; absent
-      // slots are not filled (the kernels never read them)
+      // slots are not filled and keep what an earlier call left in the pooled buffer: their
+      // contents never influence a result and are never written (include/reedsol.h;
+      // tests/test_gpu_missing_slots.py decodes after decoy stripes to check it)
       const size_t o_rec = align256(k * sb), o_out = o_rec + align256(m * sb);
       OneShotLease lease;
       if ((st = oneshot_acquire(dev, o_out + e * sb, &lease.c))) return st;

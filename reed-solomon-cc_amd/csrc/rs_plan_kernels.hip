@@ -166,7 +166,9 @@ __global__ __launch_bounds__(256) void k_pattern_tables(const uint8_t *__restric
   if (p >= o0 && p < o0 + k && !pr[p - o0]) {
     int32_t slot = 0;
     for (uint32_t i = 0; i < p - o0; i++) slot += pr[i] ? 0 : 1;
-    dv = slot < static_cast<int32_t>(max_e) ? slot : -1;
+    uint32_t have = 0;  // a NotEnoughShards stripe restores nothing: no slot of its row is written
+    for (uint32_t i = 0; i < k + m; i++) have += pr[i] ? 1 : 0;
+    dv = have >= k && slot < static_cast<int32_t>(max_e) ? slot : -1;
     make_tab_d(tq, 65535u - lm, d1, exp, log);
   }
   pre[g] = tp;

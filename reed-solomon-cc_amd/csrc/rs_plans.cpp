@@ -228,6 +228,9 @@ int get_decode_plan(int dev, uint64_t k, uint64_t m, uint64_t sb, uint32_t flags
                     std::to_string(flags) + "/" + mode + "/" + std::to_string(sb % 512 == 0) + "/" +
                     std::to_string(jit::enabled() && jit::shard_ok(sb)) + "/" +
                     std::to_string(fft_enabled() && fftnet::supports(k, m, sb)) + "/" +
+                    // the syndrome path's FFT form + generic solve need whole 4 KiB units (syndrome_block
+                    // below): a plan built for them must not serve 1 / 2 KiB-unit shards of the same pattern
+                    std::to_string(fftnet::pieces(sb) == 1 && sb % jit::kUnitBytes == 0) + "/" +
                     std::to_string(jit::max_blocks()) + "/" + std::to_string(jit::max_async_blocks()) + "/" +
                     std::to_string(fdec_mode()) + "/" + std::to_string(fdec_supports(k, m, sb, flags)) + "/" +
                     std::to_string(pdec_enabled()) + "/";

@@ -4,6 +4,8 @@ with strided stripes, and at the BASELINE c4 size (RS(200,55) 256 KiB) in full."
 import numpy as np
 import pytest
 
+from slot_contract import poison
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
@@ -95,9 +97,11 @@ def test_fft_syndrome_1k_shards(oracle, monkeypatch):
     lost = list(range(3, 200, 5))[:40]
     present[lost] = 0
     assert "syndrome+net_fft_encode" in R.reconstruct_kernel_name(k, m, sb, present)
-    d = torch.from_numpy(data).to(DEV)
-    d[:, lost] = 0
-    pr = torch.from_numpy(par).to(DEV)
+    # every missing slot holds bytes that differ from the truth everywhere (never zeros, which a
+    # GF(2)-linear code cannot see): the restored shards must not depend on them
+    shards = poison(np.concatenate([data, par], axis=1), present, seed=k + m)
+    d = torch.from_numpy(np.ascontiguousarray(shards[:, :k])).to(DEV)
+    pr = torch.from_numpy(np.ascontiguousarray(shards[:, k:])).to(DEV)
     out = torch.zeros((n, len(lost), sb), dtype=torch.uint8, device=DEV)
     R.reconstruct_batch_dev(k, m, present, d, pr, out)
     torch.cuda.synchronize()

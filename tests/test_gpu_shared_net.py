@@ -5,6 +5,8 @@ direct reconstruct and the syndrome map of a wide code."""
 import numpy as np
 import pytest
 
+from slot_contract import poison
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
@@ -48,10 +50,12 @@ def test_shared_reconstruct(oracle, shared, k, m, lost):
     par = oracle.encode_batch(k, m, data, threads=8)
     present = np.ones(k + m, np.uint8)
     present[lost] = 0
-    d = torch.from_numpy(data).to(DEV)
-    d[:, lost] = 0
+    # every missing slot holds bytes that differ from the truth everywhere (never zeros, which a
+    # GF(2)-linear code cannot see): the restored shards must not depend on them
+    shards = poison(np.concatenate([data, par], axis=1), present, seed=k + m)
+    d = torch.from_numpy(np.ascontiguousarray(shards[:, :k])).to(DEV)
     out = torch.zeros((n, len(lost), sb), dtype=torch.uint8, device=DEV)
-    R.reconstruct_batch_dev(k, m, present, d, torch.from_numpy(par).to(DEV), out)
+    R.reconstruct_batch_dev(k, m, present, d, torch.from_numpy(np.ascontiguousarray(shards[:, k:])).to(DEV), out)
     torch.cuda.synchronize()
     assert np.array_equal(out.cpu().numpy(), data[:, lost]), R.reconstruct_kernel_name(k, m, sb, present)
 
@@ -95,9 +99,11 @@ def test_shared_reconstruct_balanced_waves(oracle, shared, monkeypatch, balance,
     par = oracle.encode_batch(k, m, data, threads=8)
     present = np.ones(k + m, np.uint8)
     present[lost] = 0
-    d = torch.from_numpy(data).to(DEV)
-    d[:, lost] = 0
+    # every missing slot holds bytes that differ from the truth everywhere (never zeros, which a
+    # GF(2)-linear code cannot see): the restored shards must not depend on them
+    shards = poison(np.concatenate([data, par], axis=1), present, seed=k + m)
+    d = torch.from_numpy(np.ascontiguousarray(shards[:, :k])).to(DEV)
     out = torch.zeros((n, len(lost), sb), dtype=torch.uint8, device=DEV)
-    R.reconstruct_batch_dev(k, m, present, d, torch.from_numpy(par).to(DEV), out)
+    R.reconstruct_batch_dev(k, m, present, d, torch.from_numpy(np.ascontiguousarray(shards[:, k:])).to(DEV), out)
     torch.cuda.synchronize()
     assert np.array_equal(out.cpu().numpy(), data[:, lost]), R.reconstruct_kernel_name(k, m, sb, present)
