@@ -113,7 +113,15 @@ void rs_decoder_free(rs_decoder *dec);
  * independent; shards of one stripe are contiguous (shard stride =
  * shard_bytes); a stripe stride of 0 means packed.
  *   d_original: [n_stripes][k][shard_bytes]  (stride original_stripe_stride)
- *   d_recovery: [n_stripes][m][shard_bytes]  (stride recovery_stripe_stride) */
+ *   d_recovery: [n_stripes][m][shard_bytes]  (stride recovery_stripe_stride)
+ * Alignment, for every entry point of this section: with shards of whole 64-byte chunks
+ * (shard_bytes % 64 == 0) each device pointer and each stripe stride must be a multiple of
+ * 4 bytes, else RS_ERR_INVALID_ARGUMENT and nothing is written (rs_verify_batch_dev: d_original
+ * and its stride; its d_recovery may have any alignment). 16-byte alignment of all of them is
+ * what the hipRTC kernels and the widest table kernels need, and what the rs_*_kernel_name
+ * functions assume; a narrower layout computes the same bytes on the table kernels with
+ * narrower lanes (_nv2 at 8 bytes, _nv1 at 4), as rs_last_kernels reports. Other shard sizes
+ * (tails) run on aligned padded copies and take any alignment. tests/test_gpu_layouts.py. */
 int rs_encode_batch_dev(uint64_t original_count, uint64_t recovery_count, size_t shard_bytes, uint64_t n_stripes,
                         const void *d_original, uint64_t original_stripe_stride, void *d_recovery,
                         uint64_t recovery_stripe_stride, uint32_t flags, rs_stream_t stream);

@@ -57,6 +57,10 @@ int rs_verify_batch_dev(uint64_t k, uint64_t m, size_t sb, uint64_t n_stripes, c
     if (bad_stride == 0) bad_stride = m;
     if (orig_stride < k * sb || rec_stride < m * sb) return fail(RS_ERR_INVALID_ARGUMENT, "stripe stride too small");
     if (bad_stride < m) return fail(RS_ERR_INVALID_ARGUMENT, "bad_stride below recovery_count");
+    // what the inner encode would reject, before anything is written (d_bad below); d_recovery
+    // only feeds the compare, which takes any alignment
+    if (sb % 64 == 0 && !align_nv({reinterpret_cast<uint64_t>(d_original), orig_stride}))
+      return fail(RS_ERR_INVALID_ARGUMENT, "d_original / orig_stride must be 4-byte aligned");
     int dev;
     if ((st = current_device(&dev))) return st;
     hipStream_t s = static_cast<hipStream_t>(stream);
