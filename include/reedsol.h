@@ -170,9 +170,10 @@ int rs_reconstruct_batch_dev_patterns(uint64_t original_count, uint64_t recovery
  * write", and validates in the encode's order (n_stripes == 0: RS_OK, nothing written; a NULL
  * pointer, a stride below the row size or 0 < bad_stride < m: RS_ERR_INVALID_ARGUMENT).
  * A set flag says that the stripe is inconsistent and which recovery rows disagree with the
- * originals, not which shard is the corrupt one: one corrupt recovery shard sets one flag; one
- * corrupt original sets all m flags under the corrected arithmetic (flags == 0), because every
- * block of the encode is a multiplication by a nonzero field element.
+ * originals: one corrupt recovery shard sets one flag; one corrupt original sets all m flags
+ * under the corrected arithmetic (flags == 0), because every block of the encode is a
+ * multiplication by a nonzero field element. Which shard is the corrupt one is
+ * rs_locate_batch_dev's answer (below).
  * Slices of stripes are encoded into a scratch of at most RS_AMD_SCRATCH_CAP_MB (by the
  * encode's own kernels) and compared with the stored shards: k + 3m rows of traffic per stripe,
  * and no second parity buffer of the whole batch. */
@@ -182,6 +183,58 @@ int rs_verify_batch_dev(uint64_t original_count, uint64_t recovery_count, size_t
                         uint32_t flags, rs_stream_t stream);
 /* The path a verify takes: "<rs_encode_kernel_name>+verify_compare". */
 const char *rs_verify_kernel_name(uint64_t original_count, uint64_t recovery_count, size_t shard_bytes);
+
+/* Locate (between scrub and heal): for every stripe, name the one shard whose corruption
+ * explains every disagreement between the stored recovery shards and the originals. With
+ * flags == 0 the encode is linear over GF(2^16), parity[r] = sum_j c[r][j] * original[j] with
+ * every c[r][j] nonzero, so the syndromes S_r = encode(originals)[r] ^ stored[r] of one corrupt
+ * original j are S_r = c[r][j] * err for every r: the ratio S_1 / S_0 at one nonzero symbol names
+ * j (the k ratios c[1][j] / c[0][j] are distinct, the code being MDS), and
+ * S_r == (c[r][j] / c[0][j]) * S_0 over the whole shard for every r >= 1 confirms it.
+ * d_located (device, n_stripes int32, every one written): an index in [0, k + m), originals
+ * first, then recovery (the order of `present`), or one of the values below.
+ * d_present (device, optional): n_stripes rows of k + m flags (row stride present_stride, 0 =
+ * k + m; bytes between rows are not touched): 1 for every shard except the located one;
+ * RS_LOCATE_RECOVERY_SET: 0 at each disagreeing recovery shard; RS_LOCATE_CLEAN and
+ * RS_LOCATE_UNLOCATED: all 1. A row can be passed as it is to rs_reconstruct_batch_dev_patterns
+ * with max_e = 1: a corrupt original is restored from the other shards; a stripe whose bad
+ * shards are recovery shards has e_s = 0 and is healed by encoding it again.
+ * d_counts (device, optional): 4 words, the stripes that are clean, located to a single shard,
+ * a recovery set, unlocated. Neither input buffer is written.
+ * Guarantee: with at most one corrupt shard in a stripe and m >= 2 the answer is exact. With two
+ * corrupt shards and m >= 3 no stripe is reported as a single shard (a weight-2 and a weight-1
+ * error with equal syndromes would differ by a codeword of weight <= 3 < m + 1). With m == 2 two
+ * corrupt shards can imitate one: the code's limit. m == 1: a disagreeing stripe is
+ * RS_LOCATE_UNLOCATED. Locating more than one corrupt shard is out of scope.
+ * Accepts everything rs_verify_batch_dev accepts, validated in the same order and with the same
+ * alignment contract (any even shard_bytes, d_original and its stride 4-byte aligned when
+ * shard_bytes % 64 == 0, d_recovery at any alignment, low-rate codes, strides; n_stripes == 0:
+ * RS_OK, nothing written; NULL d_located or 0 < present_stride < k + m:
+ * RS_ERR_INVALID_ARGUMENT), except that flags must be 0, else RS_ERR_INVALID_ARGUMENT and
+ * nothing is written: under RS_FLAG_QUIRK_D1 the engine's multiply is no field multiplication
+ * (the syndromes of one error are not multiples of each other), and RS_FLAG_QUIRK_D2 leaves some
+ * originals out of the parity altogether (k > chunk, k % chunk == 0), where no parity can name
+ * them.
+ * Slices of stripes (scratch at most RS_AMD_SCRATCH_CAP_MB, tables and flags included) are
+ * encoded and compared as by rs_verify_batch_dev; stripes whose m rows all disagree are then read
+ * once more, 2m rows, by the confirm kernel. */
+#define RS_LOCATE_CLEAN (-1)        /* every recovery shard agrees */
+#define RS_LOCATE_RECOVERY_SET (-2) /* 2..m-1 recovery shards disagree, at least one agrees: the originals are
+                                       good, the disagreeing recovery shards are the bad ones */
+#define RS_LOCATE_UNLOCATED (-3)    /* all m disagree and no single original explains it (or m == 1 and it disagrees) */
+int rs_locate_batch_dev(uint64_t original_count, uint64_t recovery_count, size_t shard_bytes, uint64_t n_stripes,
+                        const void *d_original, uint64_t original_stripe_stride, const void *d_recovery,
+                        uint64_t recovery_stripe_stride, int32_t *d_located, uint8_t *d_present,
+                        uint64_t present_stride, uint64_t *d_counts, uint32_t flags, rs_stream_t stream);
+/* The path a locate takes: "<rs_encode_kernel_name>+verify_compare+locate". */
+const char *rs_locate_kernel_name(uint64_t original_count, uint64_t recovery_count, size_t shard_bytes);
+/* Host check of the locate algebra (no device): the code's coefficient ratios are distinct, and
+ * over `trials` random stripes of a few symbols per shard a corrupted original, a corrupted
+ * recovery shard, two corrupted recovery shards and (m >= 3) two corrupted originals get the
+ * answer the guarantee above states. *mismatches = wrong answers. RS_ERR_INVALID_ARGUMENT for
+ * original_count == 0. */
+int rs_locate_selftest(uint64_t original_count, uint64_t recovery_count, int trials, uint64_t seed,
+                       uint64_t *mismatches);
 
 /* -------------------------------------- host-resident batches (end to end)
  * Same layouts and semantics as the *_dev calls, but the batch lives in HOST

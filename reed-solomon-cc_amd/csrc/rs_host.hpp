@@ -1,9 +1,9 @@
 // rs_host.hpp — internal interface of the host codec (librs_amd.so): validation and
 // error reporting, plan caches, kernel selection, plans, and the entry points the
 // C ABI files (rs_batch_dev.cpp, rs_patterns.cpp, rs_lowrate.cpp, rs_host_batch.cpp,
-// rs_oneshot.cpp, rs_verify.cpp) share. Host-side mirror of root.zig's checks and error
+// rs_oneshot.cpp, rs_verify.cpp, rs_locate.cpp) share. Host-side mirror of root.zig's checks and error
 // precedence; every device computation runs in the precompiled kernels
-// (rs_kernels.hip, rs_phase_kernels.hip, rs_plan_kernels.hip) or in a hipRTC kernel (rs_jit / rs_fftnet / rs_psyn); there is no CPU compute path.
+// (rs_kernels.hip, rs_phase_kernels.hip, rs_plan_kernels.hip, rs_locate_kernels.hip) or in a hipRTC kernel (rs_jit / rs_fftnet / rs_psyn); there is no CPU compute path.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -53,6 +53,7 @@ void release_plans();      // rs_plans.cpp (+ twiddles, rs_common.cpp)
 void release_patterns();   // rs_patterns.cpp
 void release_lowrate();    // rs_lowrate.cpp
 void release_oneshot();    // rs_oneshot.cpp
+void release_locate();     // rs_locate.cpp
 size_t oneshot_pooled();   // one-shot contexts idle in the pool
 void release_host_rings(); // rs_host_batch.cpp
 

@@ -1,5 +1,5 @@
 // rs_internal.hpp — launch interface between the host codec (rs_host.hpp and the files behind it) and
-// the HIP kernels (rs_kernels.hip, rs_phase_kernels.hip, rs_plan_kernels.hip). Not part of the
+// the HIP kernels (rs_kernels.hip, rs_phase_kernels.hip, rs_plan_kernels.hip, rs_locate_kernels.hip). Not part of the
 // public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -240,6 +240,25 @@ hipError_t launch_verify_compare(const uint8_t *a, uint64_t a_stripe_stride, con
 // *count = the number of nonzero flags among [n][m] (row stride bad_stride); zeroes *count first
 hipError_t launch_verify_count(const uint8_t *bad, uint64_t bad_stride, uint64_t n, uint32_t m, uint64_t *count,
                                hipStream_t s);
+
+// Locate (rs_locate.cpp, rs_locate_kernels.hip): enc = the encode of a slice's originals
+// ([n][m][sb]), rec = the stored recovery shards, bad = launch_verify_compare's flags, packed
+// [n][m]. The classes are the values of RS_LOCATE_* (include/reedsol.h).
+constexpr int32_t kLocClean = -1, kLocRecoverySet = -2, kLocUnlocated = -3;
+// cls[s] = a final class, k + r, or a candidate original j < k with its m - 1 multiply tables in
+// tabs[s][0, m - 1). rlog [k] and dl [k][m - 1]: the plan's ratio logs; d_exp / d_log: device_tables
+hipError_t launch_locate_classify(const uint8_t *enc, uint64_t enc_stride, const uint8_t *rec, uint64_t rec_stride,
+                                  uint64_t sb, uint64_t n, uint32_t k, uint32_t m, const uint8_t *bad,
+                                  const uint16_t *rlog, const uint16_t *dl, const uint16_t *d_exp,
+                                  const uint16_t *d_log, RsTab *tabs, int32_t *cls, hipStream_t s);
+// reject[s] (zeroed by the caller) = 1 where candidate stripe s fails S_r == mul(S_0, ratio) anywhere
+hipError_t launch_locate_confirm(const uint8_t *enc, uint64_t enc_stride, const uint8_t *rec, uint64_t rec_stride,
+                                 uint64_t sb, uint64_t n, uint32_t k, uint32_t m, const int32_t *cls,
+                                 const RsTab *tabs, uint8_t *reject, hipStream_t s);
+// located [n], present rows (may be NULL) and counts[4] (may be NULL; added to, zeroed by the caller)
+hipError_t launch_locate_finish(const int32_t *cls, const uint8_t *bad, const uint8_t *reject, uint32_t k, uint32_t m,
+                                uint64_t n, int32_t *located, uint8_t *present, uint64_t present_stride,
+                                uint64_t *counts, hipStream_t s);
 
 // Engine shims (generic, in place on a single-stripe work buffer)
 hipError_t launch_engine_fft(uint8_t *work, uint64_t shard_bytes, uint64_t pos, uint64_t size, uint64_t trunc,

@@ -7,7 +7,8 @@ after the Zig error set. Everything is computed by the gfx950 HIP kernels of
 ``librs_amd.so`` through its C ABI (include/reedsol.h); there is no CPU
 fallback — without the library or a gfx950 device every call raises.
 
-Device batch API (``encode_batch_dev`` / ``reconstruct_batch_dev`` / ``verify_batch_dev``) takes
+Device batch API (``encode_batch_dev`` / ``reconstruct_batch_dev`` / ``verify_batch_dev`` /
+``locate_batch_dev``) takes
 torch tensors that already live in HBM (PyTorch is only the allocator and
 stream provider here).
 """
@@ -24,6 +25,11 @@ FLAG_CORRECTED = 0
 FLAG_QUIRK_D1 = 1
 FLAG_QUIRK_D2 = 2
 FLAG_REF_LITERAL = 3
+
+# locate_batch_dev's answers besides a shard index (include/reedsol.h)
+LOCATE_CLEAN = -1
+LOCATE_RECOVERY_SET = -2
+LOCATE_UNLOCATED = -3
 
 _STATUS_NAMES = [
     "Ok", "TooFewOriginalShards", "NotEnoughShards", "InvalidShardSize", "UnsupportedShardCount",
@@ -81,6 +87,9 @@ def lib():
                                                         vp, u32, vp]),
         "rs_verify_batch_dev": (C.c_int, [u64, u64, sz, u64, vp, u64, vp, u64, vp, u64, vp, u32, vp]),
         "rs_verify_kernel_name": (C.c_char_p, [u64, u64, sz]),
+        "rs_locate_batch_dev": (C.c_int, [u64, u64, sz, u64, vp, u64, vp, u64, vp, vp, u64, vp, u32, vp]),
+        "rs_locate_kernel_name": (C.c_char_p, [u64, u64, sz]),
+        "rs_locate_selftest": (C.c_int, [u64, u64, C.c_int, u64, vp]),
         "rs_encode_batch_host": (C.c_int, [u64, u64, sz, u64, vp, u64, vp, u64, u32]),
         "rs_reconstruct_batch_host": (C.c_int, [u64, u64, sz, u64, vp, vp, u64, vp, u64, vp, u64, u32]),
         "rs_encode_batch_host_multi": (C.c_int, [u64, u64, sz, u64, vp, u64, vp, u64, u32, vp, C.c_int]),
@@ -302,6 +311,47 @@ def verify_batch_dev(original_count: int, recovery_count: int, data, parity, bad
 def verify_kernel_name(k, m, shard_bytes) -> str:
     """Path of verify_batch_dev for these arguments (include/reedsol.h)."""
     return lib().rs_verify_kernel_name(k, m, shard_bytes).decode()
+
+
+def locate_batch_dev(original_count: int, recovery_count: int, data, parity, located=None, present=None,
+                     counts=None, stream=None, flags: int = FLAG_CORRECTED):
+    """Between scrub and heal: data [n, k, sb] and stored parity [n, m, sb] (uint8 CUDA tensors,
+    last two dimensions contiguous) -> located, a torch.int32 tensor [n] (allocated when None):
+    the index in [0, k + m) of the one shard whose corruption explains every disagreement
+    (originals first, then recovery), or LOCATE_CLEAN / LOCATE_RECOVERY_SET / LOCATE_UNLOCATED.
+    present: optional uint8 CUDA tensor [n, k + m] (its row stride may exceed k + m), receives the
+    rows reconstruct_batch_dev_patterns takes (0 at the located shard). counts: optional int64 CUDA
+    tensor of 4 elements: clean, single shard, recovery set, unlocated. flags must be 0
+    (include/reedsol.h). Asynchronous on `stream`; returns located."""
+    n, k, sb = data.shape
+    assert k == original_count and parity.shape == (n, recovery_count, sb)
+    assert data.is_cuda and parity.is_cuda
+    assert n == 0 or (data[0].is_contiguous() and parity[0].is_contiguous())
+    if located is None:
+        import torch
+        located = torch.empty((n,), dtype=torch.int32, device=data.device)
+    assert located.is_cuda and located.shape == (n,) and located.is_contiguous()
+    if present is not None:
+        assert present.is_cuda and present.shape == (n, k + recovery_count) and (n == 0 or present[0].is_contiguous())
+    _check(lib().rs_locate_batch_dev(
+        original_count, recovery_count, sb, n, C.c_void_p(data.data_ptr()), data.stride(0),
+        C.c_void_p(parity.data_ptr()), parity.stride(0), C.c_void_p(located.data_ptr()),
+        C.c_void_p(present.data_ptr()) if present is not None else None,
+        present.stride(0) if present is not None else 0,
+        C.c_void_p(counts.data_ptr()) if counts is not None else None, flags, _stream_handle(stream)))
+    return located
+
+
+def locate_kernel_name(k, m, shard_bytes) -> str:
+    """Path of locate_batch_dev for these arguments (include/reedsol.h)."""
+    return lib().rs_locate_kernel_name(k, m, shard_bytes).decode()
+
+
+def locate_selftest(k, m, trials=8, seed=1) -> int:
+    """Host check of the locate algebra (distinct ratios, every outcome): wrong answers."""
+    bad = C.c_uint64()
+    _check(lib().rs_locate_selftest(k, m, trials, seed, C.byref(bad)))
+    return bad.value
 
 
 def encode_batch_host(original_count: int, recovery_count: int, data, parity, flags: int = FLAG_CORRECTED):

@@ -3,6 +3,9 @@
   (a) encode          rs_encode_batch_dev into a spare parity buffer
   (b) encode+compare  (a), then a per-shard `any` of spare != parity in torch
   (c) verify          rs_verify_batch_dev
+  (d) locate_clean    rs_locate_batch_dev on the clean batch (k + 3m rows, as the verify)
+  (e) locate_corrupt  rs_locate_batch_dev with one corrupt original in every stripe (every stripe
+                      is a candidate: 2m more rows for the confirm, (k + 5m) / (k + 3m) of (c)'s traffic)
 The legs alternate in one process; each timed window is warmed, ends in a device synchronise
 and lasts at least --window seconds. The set is repeated --sets times; per leg the median and
 the min-max spread of the per-call times are printed as one JSON line per shape.
@@ -58,7 +61,26 @@ def bench_shape(k, m, sb, n, sets, min_window, dev):
     assert torch.equal(leg_b().to(torch.uint8), leg_c()) and int(leg_c().sum().item()) == 1
     parity[n - 1, m - 1, sb - 1] ^= 1
 
-    legs = {"encode": leg_a, "encode+compare": leg_b, "verify": leg_c}
+    # locate: the clean batch, and a copy with one flipped bit in one original of every stripe
+    located = torch.empty((n,), dtype=torch.int32, device=dev)
+    counts = torch.zeros(4, dtype=torch.int64, device=dev)
+    broken = data.clone()
+    idx = torch.arange(n, device=dev)
+    broken[idx, idx % k, (idx * 7919) % sb] ^= 1
+
+    def leg_d():
+        return R.locate_batch_dev(k, m, data, parity, located=located, counts=counts)
+
+    def leg_e():
+        return R.locate_batch_dev(k, m, broken, parity, located=located, counts=counts)
+
+    assert bool((leg_d() == R.LOCATE_CLEAN).all().item()) and counts.tolist() == [n, 0, 0, 0]
+    want = (idx % k).to(torch.int32) if m >= 2 else torch.full_like(located, R.LOCATE_UNLOCATED)
+    assert torch.equal(leg_e(), want)
+    locate_kernels = R.last_kernels()
+
+    legs = {"encode": leg_a, "encode+compare": leg_b, "verify": leg_c, "locate_clean": leg_d,
+            "locate_corrupt": leg_e}
     reps = {}
     for name, fn in legs.items():  # warm, and size the windows
         fn()
@@ -77,6 +99,11 @@ def bench_shape(k, m, sb, n, sets, min_window, dev):
     res["verify_beats_encode+compare_beyond_spreads"] = \
         b["median_ms"] - c["median_ms"] > b["spread_ms"] + c["spread_ms"]
     res["verify_over_encode"] = round(c["median_ms"] / res["legs"]["encode"]["median_ms"], 4)
+    res["locate_kernels"] = locate_kernels
+    res["locate_kernel_name"] = R.locate_kernel_name(k, m, sb)
+    res["locate_clean_over_verify"] = round(res["legs"]["locate_clean"]["median_ms"] / c["median_ms"], 4)
+    res["locate_corrupt_over_verify"] = round(res["legs"]["locate_corrupt"]["median_ms"] / c["median_ms"], 4)
+    res["locate_corrupt_traffic_over_verify"] = round((k + 5 * m) / (k + 3 * m), 4)
     return res
 
 
