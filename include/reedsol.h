@@ -236,6 +236,53 @@ const char *rs_locate_kernel_name(uint64_t original_count, uint64_t recovery_cou
 int rs_locate_selftest(uint64_t original_count, uint64_t recovery_count, int trials, uint64_t seed,
                        uint64_t *mismatches);
 
+/* Update (the small write): some originals of a stripe change and its stored recovery shards
+ * follow in place, without the other originals. With flags == 0 the encode is linear over
+ * GF(2^16), parity[r] = sum_j c[r][j] * original[j], so changing original j from old to new
+ * changes recovery shard r by exactly c[r][j] * (old ^ new): after the call d_recovery holds, byte
+ * for byte, what rs_encode_batch_dev writes for the new originals (if it held that for the old
+ * ones). 2u + 2m shard rows of traffic per stripe for u changed originals (u + 2m in delta form)
+ * instead of the encode's k + m.
+ * d_index (device): n_stripes rows of max_u words (row stride index_stride, in words; 0 =
+ * max_u). Slot i of stripe s names the original that changed (< k) or holds RS_UPDATE_NONE; empty
+ * slots may sit anywhere in a row, and a row of all RS_UPDATE_NONE leaves its stripe untouched.
+ * d_old, d_new (device): [n_stripes][max_u][shard_bytes] with one stripe stride,
+ * change_stripe_stride (0 = packed); slot i's shard is at s * stride + i * shard_bytes, and the
+ * shards of empty slots are never read. d_old == NULL is the delta form: d_new already holds
+ * old ^ new (what a node receives when the data lives elsewhere).
+ * d_recovery (device): [n_stripes][m][shard_bytes], updated in place:
+ * recovery[r] ^= sum_i c[r][index_i] * (old_i ^ new_i). No byte outside the m rows of a stripe is
+ * written (stride padding, rows past the batch), and d_index, d_old and d_new are never written.
+ * d_status (device, n_stripes int32, may be NULL; every entry written): RS_OK;
+ * RS_ERR_INVALID_SHARD_INDEX if any slot is >= k and not RS_UPDATE_NONE (checked first);
+ * RS_ERR_DUPLICATE_SHARD_INDEX if two slots name the same original. A stripe that is not RS_OK has
+ * no byte of its parity written; the other stripes of the batch are updated.
+ * Validated on the host before any device call, in this order: original_count == 0
+ * (RS_ERR_TOO_FEW_ORIGINAL_SHARDS); the encode's checks of the counts and shard_bytes; n_stripes
+ * == 0 or max_u == 0: RS_OK, nothing written; then RS_ERR_INVALID_ARGUMENT for a NULL d_index,
+ * d_new or d_recovery, max_u > k, a stride below its row size, flags != 0 (as for
+ * rs_locate_batch_dev: under RS_FLAG_QUIRK_D1 the multiply is no field multiplication, and
+ * RS_FLAG_QUIRK_D2 leaves originals out of the parity), with shard_bytes % 64 == 0 a d_old, d_new,
+ * d_recovery or stripe stride of theirs that is no multiple of 4, and a d_old or d_new range that
+ * overlaps [d_recovery, d_recovery + n_stripes * stride) (the update would read what it writes).
+ * Other shard sizes (tails) take any alignment, on byte accesses; low-rate codes are served.
+ * Slices of stripes (scratch at most RS_AMD_SCRATCH_CAP_MB: 96 * max_u * m bytes of multiply
+ * tables per stripe, built on the device) run k_update_prepare, then k_update_apply (16-byte,
+ * dword or byte accesses by what every buffer, stride and shard_bytes allow, as rs_last_kernels
+ * reports: _x16 / _x4 / _x1). Up to 4 changed originals of a stripe are applied in one pass over
+ * its parity; every further 4 cost one more read and write of it. */
+#define RS_UPDATE_NONE 0xFFFFFFFFu /* an empty slot of a d_index row */
+int rs_update_batch_dev(uint64_t original_count, uint64_t recovery_count, size_t shard_bytes, uint64_t n_stripes,
+                        uint32_t max_u, const uint32_t *d_index, uint64_t index_stride, const void *d_old,
+                        const void *d_new, uint64_t change_stripe_stride, void *d_recovery,
+                        uint64_t recovery_stripe_stride, int32_t *d_status, uint32_t flags, rs_stream_t stream);
+/* Host check of the update algebra (no device): over `trials` random stripes of a few symbols per
+ * shard, 1..min(max_u, k) distinct originals change and stored ^ sum c[r][j] * delta must equal
+ * the scalar encode of the new originals. *mismatches = wrong symbols (or 1 for a zero
+ * coefficient). RS_ERR_INVALID_ARGUMENT for original_count == 0. */
+int rs_update_selftest(uint64_t original_count, uint64_t recovery_count, uint32_t max_u, int trials, uint64_t seed,
+                       uint64_t *mismatches);
+
 /* -------------------------------------- host-resident batches (end to end)
  * Same layouts and semantics as the *_dev calls, but the batch lives in HOST
  * memory: the library streams it through HBM in slices on a 2-slot

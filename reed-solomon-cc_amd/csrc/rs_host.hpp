@@ -1,9 +1,9 @@
 // rs_host.hpp — internal interface of the host codec (librs_amd.so): validation and
 // error reporting, plan caches, kernel selection, plans, and the entry points the
 // C ABI files (rs_batch_dev.cpp, rs_patterns.cpp, rs_lowrate.cpp, rs_host_batch.cpp,
-// rs_oneshot.cpp, rs_verify.cpp, rs_locate.cpp) share. Host-side mirror of root.zig's checks and error
+// rs_oneshot.cpp, rs_verify.cpp, rs_locate.cpp, rs_update.cpp) share. Host-side mirror of root.zig's checks and error
 // precedence; every device computation runs in the precompiled kernels
-// (rs_kernels.hip, rs_phase_kernels.hip, rs_plan_kernels.hip, rs_locate_kernels.hip) or in a hipRTC kernel (rs_jit / rs_fftnet / rs_psyn); there is no CPU compute path.
+// (rs_kernels.hip, rs_phase_kernels.hip, rs_plan_kernels.hip, rs_locate_kernels.hip, rs_update_kernels.hip) or in a hipRTC kernel (rs_jit / rs_fftnet / rs_psyn); there is no CPU compute path.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -54,6 +54,7 @@ void release_patterns();   // rs_patterns.cpp
 void release_lowrate();    // rs_lowrate.cpp
 void release_oneshot();    // rs_oneshot.cpp
 void release_locate();     // rs_locate.cpp
+void release_update();     // rs_update.cpp
 size_t oneshot_pooled();   // one-shot contexts idle in the pool
 void release_host_rings(); // rs_host_batch.cpp
 
@@ -333,6 +334,11 @@ uint32_t pdec_after();
 size_t pdec_queue();
 // admit the pattern `key` of code (dev, k, m) to the budget (true if already admitted)
 bool pdec_admit(int dev, uint64_t k, uint64_t m, const std::string &key);
+// cl[j * m + r] = log c[r][j] in [0, 65535), the encode's coefficients (parity[r] = sum_j c[r][j]
+// * original[j] under the corrected arithmetic), from the scalar encode of unit vectors (the
+// low-rate encode for low-rate codes). false if a coefficient is zero (never in an MDS code).
+// rs_update.cpp; locate derives its ratios from it.
+bool coef_logs(uint64_t k, uint64_t m, std::vector<uint16_t> &cl);
 // exp, log, log_walsh in HBM (384 KiB per device)
 int device_tables(int dev, const uint16_t **exp, const uint16_t **log, const uint16_t **lw);
 

@@ -1,6 +1,6 @@
 // rs_internal.hpp — launch interface between the host codec (rs_host.hpp and the files behind it) and
-// the HIP kernels (rs_kernels.hip, rs_phase_kernels.hip, rs_plan_kernels.hip, rs_locate_kernels.hip). Not part of the
-// public ABI.
+// the HIP kernels (rs_kernels.hip, rs_phase_kernels.hip, rs_plan_kernels.hip, rs_locate_kernels.hip,
+// rs_update_kernels.hip). Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -259,6 +259,24 @@ hipError_t launch_locate_confirm(const uint8_t *enc, uint64_t enc_stride, const 
 hipError_t launch_locate_finish(const int32_t *cls, const uint8_t *bad, const uint8_t *reject, uint32_t k, uint32_t m,
                                 uint64_t n, int32_t *located, uint8_t *present, uint64_t present_stride,
                                 uint64_t *counts, hipStream_t s);
+
+// Update (rs_update.cpp, rs_update_kernels.hip): index rows [n][max_u] of changed originals
+// (kUpdateNone = RS_UPDATE_NONE: an empty slot), cl [k][m] = the plan's log c[r][j]. Per stripe:
+// status (may be NULL; 0, kUpdateInvalidIndex or kUpdateDuplicateIndex, the ABI's values), the
+// live slots list[s][0, live[s]) as slot << 16 | j (live[s] = 0 for a rejected stripe) and their
+// multiply tables tabs[s][max_u][m].
+constexpr uint32_t kUpdateNone = 0xFFFFFFFFu;
+constexpr int32_t kUpdateInvalidIndex = 7, kUpdateDuplicateIndex = 8;
+hipError_t launch_update_prepare(const uint32_t *index, uint64_t index_stride, uint32_t max_u, uint64_t n, uint32_t k,
+                                 uint32_t m, const uint16_t *cl, const uint16_t *d_exp, const uint16_t *d_log,
+                                 RsTab *tabs, uint32_t *list, uint32_t *live, int32_t *status, hipStream_t s);
+// rec[s][r] ^= sum over the live slots of c[r][j] * (d_old ^ d_new)[s][slot], in place (d_old may
+// be NULL: d_new holds the deltas). 16-byte accesses when every buffer, both strides and sb allow
+// them, dwords when all are 4-byte aligned, bytes otherwise; the launch record names the variant
+// (k_update_apply_x16 / _x4 / _x1, then _t<slots of a tile>).
+hipError_t launch_update_apply(const uint8_t *d_old, const uint8_t *d_new, uint64_t change_stride, uint8_t *rec,
+                               uint64_t rec_stride, uint64_t sb, uint64_t n, uint32_t m, uint32_t max_u,
+                               const uint32_t *list, const uint32_t *live, const RsTab *tabs, hipStream_t s);
 
 // Engine shims (generic, in place on a single-stripe work buffer)
 hipError_t launch_engine_fft(uint8_t *work, uint64_t shard_bytes, uint64_t pos, uint64_t size, uint64_t trunc,

@@ -15,24 +15,16 @@ static_assert(RS_LOCATE_CLEAN == kLocClean && RS_LOCATE_RECOVERY_SET == kLocReco
                   RS_LOCATE_UNLOCATED == kLocUnlocated,
               "the kernels' classes are the ABI's");
 
-// dl[j * (m - 1) + r - 1] = log(c[r][j] / c[0][j]) in [0, 65535), r in [1, m): c from the scalar
-// encode of unit vectors (symbol 1 is the field's one). false if a coefficient is zero or two
-// originals share the ratio of row 1 (neither happens in an MDS code).
+// dl[j * (m - 1) + r - 1] = log(c[r][j] / c[0][j]) in [0, 65535), r in [1, m): from the logs of the
+// coefficients c (coef_logs). false if a coefficient is zero or two originals share the ratio of
+// row 1 (neither happens in an MDS code).
 bool ratio_logs(uint64_t k, uint64_t m, std::vector<uint16_t> &dl) {
-  const Tables &t = tables();
-  const bool low = is_low_rate(k, m);
-  std::vector<uint16_t> in(k, 0), out(m);
+  std::vector<uint16_t> cl;
+  if (!coef_logs(k, m, cl)) return false;
   dl.assign(k * (m - 1), 0);
-  for (uint64_t j = 0; j < k; j++) {
-    in[j] = 1;
-    if (low) scalar_encode_low(in.data(), k, m, false, out.data());
-    else scalar_encode(in.data(), k, m, false, false, out.data());
-    in[j] = 0;
-    for (uint64_t r = 0; r < m; r++)
-      if (out[r] == 0) return false;
+  for (uint64_t j = 0; j < k; j++)
     for (uint64_t r = 1; r < m; r++)
-      dl[j * (m - 1) + r - 1] = static_cast<uint16_t>((uint32_t(t.log[out[r]]) + kModulus - t.log[out[0]]) % kModulus);
-  }
+      dl[j * (m - 1) + r - 1] = static_cast<uint16_t>((uint32_t(cl[j * m + r]) + kModulus - cl[j * m]) % kModulus);
   if (m < 2) return true;
   std::vector<uint16_t> first(k);
   for (uint64_t j = 0; j < k; j++) first[j] = dl[j * (m - 1)];

@@ -22,103 +22,21 @@
 #include <algorithm>
 
 #include "rs_device.hpp"
+#include "rs_device_lanes.hpp"
 #include "rs_internal.hpp"
 
 namespace rs {
 namespace {
 
+using dev::build_tab;
+using dev::Lanes;
+using dev::ld_xor;
+using dev::ld_xor_tail;
 using dev::Sym;
 using dev::Tab;
 
 constexpr uint32_t kLocateSeg = 16384;  // as k_verify_compare: a multiple of 16 and of 64
 constexpr uint32_t kNoLog = 0xFFFFFFFFu;
-
-// ---- loads of one lane's dword pairs of S = a ^ b. a / b point at the lane's low bytes; the high
-// bytes lie 32 further (one 64-byte chunk). MODE 2: 16-byte loads (NV 4), 1: dwords, 0: bytes.
-template <int MODE>
-struct Lanes {
-  static constexpr int NV = MODE == 2 ? 4 : 1;
-};
-
-__device__ __forceinline__ uint32_t ld4_bytes(const uint8_t *p) {
-  return static_cast<uint32_t>(p[0]) | static_cast<uint32_t>(p[1]) << 8 | static_cast<uint32_t>(p[2]) << 16 |
-         static_cast<uint32_t>(p[3]) << 24;
-}
-
-template <int MODE>
-__device__ __forceinline__ void ld_xor(Sym<Lanes<MODE>::NV> &s, const uint8_t *__restrict__ a,
-                                       const uint8_t *__restrict__ b) {
-  if constexpr (MODE == 2) {
-    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-    const v4u al = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(a));
-    const v4u ah = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(a + 32));
-    const v4u bl = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(b));
-    const v4u bh = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(b + 32));
-#pragma unroll
-    for (int v = 0; v < 4; v++) {
-      s.l[v] = al[v] ^ bl[v];
-      s.h[v] = ah[v] ^ bh[v];
-    }
-  } else if constexpr (MODE == 1) {
-    s.l[0] = *reinterpret_cast<const uint32_t *>(a) ^ *reinterpret_cast<const uint32_t *>(b);
-    s.h[0] = *reinterpret_cast<const uint32_t *>(a + 32) ^ *reinterpret_cast<const uint32_t *>(b + 32);
-  } else {
-    s.l[0] = ld4_bytes(a) ^ ld4_bytes(b);
-    s.h[0] = ld4_bytes(a + 32) ^ ld4_bytes(b + 32);
-  }
-}
-
-// The tail chunk (k_tail_pack's layout): t = sb % 64 bytes at `whole`, h = t / 2 symbols, low
-// bytes at [0, h), high bytes at [h, t). Lane `lane` (< 8) takes symbols [4 lane, 4 lane + 4).
-__device__ __forceinline__ void ld_xor_tail(Sym<1> &s, const uint8_t *__restrict__ a, const uint8_t *__restrict__ b,
-                                            uint32_t h, uint32_t lane) {
-  s.l[0] = s.h[0] = 0;
-#pragma unroll
-  for (uint32_t q = 0; q < 4; q++) {
-    const uint32_t i = 4 * lane + q;
-    if (i < h) {
-      s.l[0] |= static_cast<uint32_t>(a[i] ^ b[i]) << (8 * q);
-      s.h[0] |= static_cast<uint32_t>(a[h + i] ^ b[h + i]) << (8 * q);
-    }
-  }
-}
-
-// rs_gf.cpp make_tab (corrected multiply) on the device: the v_perm tables of the multiplication
-// by exp[lm], from the images of the 16 basis symbols 1 << b.
-__device__ void build_tab(RsTab *out, uint32_t lm, const uint16_t *__restrict__ d_exp,
-                          const uint16_t *__restrict__ d_log) {
-  uint32_t img[16];
-#pragma unroll
-  for (int b = 0; b < 16; b++) {
-    const uint32_t sum = static_cast<uint32_t>(d_log[1u << b]) + lm;
-    img[b] = d_exp[(sum + (sum >> 16)) & 0xFFFFu];  // rs_gf.hpp add_mod
-  }
-  constexpr int kOff[6] = {0, 3, 6, 8, 11, 14}, kBits[6] = {3, 3, 2, 3, 3, 2}, kSlot[6] = {0, 2, 4, 5, 7, 9};
-  uint32_t lo[10], hi[10];
-#pragma unroll
-  for (int i = 0; i < 10; i++) lo[i] = hi[i] = 0;
-#pragma unroll
-  for (int f = 0; f < 6; f++) {
-#pragma unroll
-    for (uint32_t v = 0; v < (1u << kBits[f]); v++) {
-      uint32_t p = 0;
-#pragma unroll
-      for (int b = 0; b < kBits[f]; b++)
-        if (v >> b & 1) p ^= img[kOff[f] + b];
-      const int w = kSlot[f] + (v >> 2), sh = 8 * (v & 3);
-      lo[w] |= (p & 0xFFu) << sh;
-      hi[w] |= (p >> 8) << sh;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 10; i++) {
-    out->lo[i] = lo[i];
-    out->hi[i] = hi[i];
-  }
-  out->flags = 0;
-  out->log_m = lm;
-  out->pad[0] = out->pad[1] = 0;
-}
 
 // ============================================================ classify + candidate
 // cls[s]: kLocClean / kLocRecoverySet / kLocUnlocated, k + r (one recovery shard disagrees), or a

@@ -8,7 +8,7 @@ after the Zig error set. Everything is computed by the gfx950 HIP kernels of
 fallback — without the library or a gfx950 device every call raises.
 
 Device batch API (``encode_batch_dev`` / ``reconstruct_batch_dev`` / ``verify_batch_dev`` /
-``locate_batch_dev``) takes
+``locate_batch_dev`` / ``update_batch_dev``) takes
 torch tensors that already live in HBM (PyTorch is only the allocator and
 stream provider here).
 """
@@ -30,6 +30,9 @@ FLAG_REF_LITERAL = 3
 LOCATE_CLEAN = -1
 LOCATE_RECOVERY_SET = -2
 LOCATE_UNLOCATED = -3
+
+# an empty slot of update_batch_dev's index rows (include/reedsol.h RS_UPDATE_NONE)
+UPDATE_NONE = 0xFFFFFFFF
 
 _STATUS_NAMES = [
     "Ok", "TooFewOriginalShards", "NotEnoughShards", "InvalidShardSize", "UnsupportedShardCount",
@@ -90,6 +93,8 @@ def lib():
         "rs_locate_batch_dev": (C.c_int, [u64, u64, sz, u64, vp, u64, vp, u64, vp, vp, u64, vp, u32, vp]),
         "rs_locate_kernel_name": (C.c_char_p, [u64, u64, sz]),
         "rs_locate_selftest": (C.c_int, [u64, u64, C.c_int, u64, vp]),
+        "rs_update_batch_dev": (C.c_int, [u64, u64, sz, u64, u32, vp, u64, vp, vp, u64, vp, u64, vp, u32, vp]),
+        "rs_update_selftest": (C.c_int, [u64, u64, u32, C.c_int, u64, vp]),
         "rs_encode_batch_host": (C.c_int, [u64, u64, sz, u64, vp, u64, vp, u64, u32]),
         "rs_reconstruct_batch_host": (C.c_int, [u64, u64, sz, u64, vp, vp, u64, vp, u64, vp, u64, u32]),
         "rs_encode_batch_host_multi": (C.c_int, [u64, u64, sz, u64, vp, u64, vp, u64, u32, vp, C.c_int]),
@@ -351,6 +356,47 @@ def locate_selftest(k, m, trials=8, seed=1) -> int:
     """Host check of the locate algebra (distinct ratios, every outcome): wrong answers."""
     bad = C.c_uint64()
     _check(lib().rs_locate_selftest(k, m, trials, seed, C.byref(bad)))
+    return bad.value
+
+
+def update_batch_dev(original_count: int, recovery_count: int, index, new, parity, old=None, status=None,
+                     stream=None, flags: int = FLAG_CORRECTED):
+    """The small write: parity [n, m, sb] follows the originals that changed, in place.
+    index: CUDA tensor [n, max_u] of 4-byte integers (torch.int32 or torch.uint32; its row stride
+    may exceed max_u): slot i of stripe s names the original that changed, or holds UPDATE_NONE
+    (-1 as int32). new, old: uint8 CUDA tensors [n, max_u, sb] with one stripe stride (last two
+    dimensions contiguous), the shards of the named originals after and before the change;
+    old=None is the delta form: new already holds old ^ new. Shards of empty slots are not read.
+    status: optional int32 CUDA tensor [n] (allocated when None): 0, 7 (an index >= k) or 8 (an
+    index named twice); such a stripe's parity is not written. flags must be 0
+    (include/reedsol.h). Asynchronous on `stream`; returns status."""
+    n, max_u = index.shape
+    m = recovery_count
+    assert parity.is_cuda and parity.dim() == 3 and parity.shape[:2] == (n, m)
+    sb = parity.shape[2]
+    assert index.is_cuda and index.element_size() == 4 and not index.is_floating_point()
+    assert new.is_cuda and new.shape == (n, max_u, sb)
+    assert n == 0 or (parity[0].is_contiguous() and index[0].is_contiguous())
+    assert n == 0 or max_u == 0 or new[0].is_contiguous()
+    if old is not None:
+        assert old.is_cuda and old.shape == new.shape and (n == 0 or max_u == 0 or old[0].is_contiguous())
+        assert n <= 1 or old.stride(0) == new.stride(0), "old and new share one stripe stride"
+    if status is None:
+        import torch
+        status = torch.empty((n,), dtype=torch.int32, device=parity.device)
+    assert status.is_cuda and status.shape == (n,) and status.is_contiguous()
+    _check(lib().rs_update_batch_dev(
+        original_count, m, sb, n, max_u, C.c_void_p(index.data_ptr()), index.stride(0),
+        C.c_void_p(old.data_ptr()) if old is not None else None, C.c_void_p(new.data_ptr()), new.stride(0),
+        C.c_void_p(parity.data_ptr()), parity.stride(0), C.c_void_p(status.data_ptr()), flags,
+        _stream_handle(stream)))
+    return status
+
+
+def update_selftest(k, m, max_u=4, trials=8, seed=1) -> int:
+    """Host check of the update algebra (stored ^ sum c * delta == encode(new)): wrong symbols."""
+    bad = C.c_uint64()
+    _check(lib().rs_update_selftest(k, m, max_u, trials, seed, C.byref(bad)))
     return bad.value
 
 
