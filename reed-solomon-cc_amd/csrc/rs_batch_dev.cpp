@@ -16,10 +16,9 @@ namespace host {
 // slices of <= 1 GiB, then the outputs are unpadded.
 
 int pad_shards(const uint8_t *src, uint64_t src_stripe_stride, uint64_t sb, uint8_t *dst, uint64_t dst_stripe_stride,
-               uint64_t psb, uint64_t n, hipStream_t s) {
+               uint64_t n, hipStream_t s) {
   const uint64_t whole = sb / 64 * 64;
   if (whole) HIP_TRY(hipMemcpy2DAsync(dst, dst_stripe_stride, src, src_stripe_stride, whole, n, hipMemcpyDeviceToDevice, s));
-  (void)psb;
   HIP_TRY(launch_tail_pack(src, src_stripe_stride, dst, dst_stripe_stride, sb, n, false, s));
   return RS_OK;
 }
@@ -32,48 +31,50 @@ int unpad_shards(const uint8_t *src, uint64_t src_stripe_stride, uint64_t sb, ui
   return RS_OK;
 }
 
+int pad_group(const uint8_t *src, uint64_t src_stripe_stride, uint64_t sb, uint64_t rows, const uint8_t *present,
+              uint8_t *dst, uint64_t psb, uint64_t n, hipStream_t s) {
+  for (uint64_t i = 0; i < rows; i++)
+    if (!present || present[i])
+      if (int st = pad_shards(src + i * sb, src_stripe_stride, sb, dst + i * psb, rows * psb, n, s)) return st;
+  return RS_OK;
+}
+
+int unpad_group(const uint8_t *src, uint64_t psb, uint64_t rows, uint8_t *dst, uint64_t dst_stripe_stride, uint64_t sb,
+                uint64_t n, hipStream_t s) {
+  for (uint64_t j = 0; j < rows; j++)
+    if (int st = unpad_shards(src + j * psb, rows * psb, sb, dst + j * sb, dst_stripe_stride, n, s)) return st;
+  return RS_OK;
+}
+
 int encode_tail(uint64_t k, uint64_t m, uint64_t sb, uint64_t n, const uint8_t *orig, uint64_t ostride, uint8_t *rec,
                 uint64_t rstride, uint32_t flags, hipStream_t s) {
   const uint64_t psb = (sb + 63) / 64 * 64;
-  const uint64_t cap = std::max<uint64_t>(1, std::min<uint64_t>(n, kTailSliceBytes / ((k + m) * psb)));
-  void *buf = nullptr;
-  HIP_TRY(dev_malloc_async(&buf, cap * (k + m) * psb, s));
-  uint8_t *pin = static_cast<uint8_t *>(buf), *pout = pin + cap * k * psb;
-  int st = RS_OK;
-  for (uint64_t s0 = 0; st == RS_OK && s0 < n; s0 += cap) {
-    const uint64_t cnt = std::min(cap, n - s0);
-    for (uint64_t i = 0; st == RS_OK && i < k; i++)
-      st = pad_shards(orig + s0 * ostride + i * sb, ostride, sb, pin + i * psb, k * psb, psb, cnt, s);
+  const uint64_t cap = fit_stripes(n, kTailSliceBytes, (k + m) * psb);
+  return in_scratch_slices(n, cap, cap * (k + m) * psb, s, [&](uint64_t s0, uint64_t cnt, uint8_t *pin) {
+    uint8_t *pout = pin + cap * k * psb;
+    int st = pad_group(orig + s0 * ostride, ostride, sb, k, nullptr, pin, psb, cnt, s);
     if (st == RS_OK) st = rs_encode_batch_dev(k, m, psb, cnt, pin, 0, pout, 0, flags, s);
-    for (uint64_t r = 0; st == RS_OK && r < m; r++)
-      st = unpad_shards(pout + r * psb, m * psb, sb, rec + s0 * rstride + r * sb, rstride, cnt, s);
-  }
-  (void)hipFreeAsync(buf, s);
-  return st;
+    if (st == RS_OK) st = unpad_group(pout, psb, m, rec + s0 * rstride, rstride, sb, cnt, s);
+    return st;
+  });
 }
 
 int reconstruct_tail(uint64_t k, uint64_t m, uint64_t sb, uint64_t n, const uint8_t *present, uint64_t e,
                      const uint8_t *orig, uint64_t ostride, const uint8_t *rec, uint64_t rstride, uint8_t *out,
                      uint64_t outstride, uint32_t flags, hipStream_t s) {
   const uint64_t psb = (sb + 63) / 64 * 64;
-  const uint64_t cap = std::max<uint64_t>(1, std::min<uint64_t>(n, kTailSliceBytes / ((k + m + e) * psb)));
-  void *buf = nullptr;
-  HIP_TRY(dev_malloc_async(&buf, cap * (k + m + e) * psb, s));
-  uint8_t *po = static_cast<uint8_t *>(buf), *pr = po + cap * k * psb, *pout = pr + cap * m * psb;
-  int st = RS_OK;
-  for (uint64_t s0 = 0; st == RS_OK && s0 < n; s0 += cap) {
-    const uint64_t cnt = std::min(cap, n - s0);
-    for (uint64_t i = 0; st == RS_OK && i < k; i++)  // only present shards are read
-      if (present[i]) st = pad_shards(orig + s0 * ostride + i * sb, ostride, sb, po + i * psb, k * psb, psb, cnt, s);
-    for (uint64_t i = 0; st == RS_OK && i < m; i++)
-      if (present[k + i])
-        st = pad_shards(rec + s0 * rstride + i * sb, rstride, sb, pr + i * psb, m * psb, psb, cnt, s);
+  const uint64_t cap = fit_stripes(n, kTailSliceBytes, (k + m + e) * psb);
+  if (!orig) orig = rec;  // never dereferenced for absent shards
+  if (!rec) rec = orig;
+  return in_scratch_slices(n, cap, cap * (k + m + e) * psb, s, [&](uint64_t s0, uint64_t cnt, uint8_t *po) {
+    uint8_t *pr = po + cap * k * psb, *pout = pr + cap * m * psb;
+    // only present shards are read
+    int st = pad_group(orig + s0 * ostride, ostride, sb, k, present, po, psb, cnt, s);
+    if (st == RS_OK) st = pad_group(rec + s0 * rstride, rstride, sb, m, present + k, pr, psb, cnt, s);
     if (st == RS_OK) st = rs_reconstruct_batch_dev(k, m, psb, cnt, present, po, 0, pr, 0, pout, 0, flags, s);
-    for (uint64_t j = 0; st == RS_OK && j < e; j++)
-      st = unpad_shards(pout + j * psb, e * psb, sb, out + s0 * outstride + j * sb, outstride, cnt, s);
-  }
-  (void)hipFreeAsync(buf, s);
-  return st;
+    if (st == RS_OK) st = unpad_group(pout, psb, e, out + s0 * outstride, outstride, sb, cnt, s);
+    return st;
+  });
 }
 
 }  // namespace host
@@ -154,24 +155,16 @@ int rs_encode_batch_dev(uint64_t k, uint64_t m, size_t sb, uint64_t n_stripes, c
       HIP_TRY(launch_encode(kc, a, s));
       return RS_OK;
     }
-    const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_stripes, kScratchCap / (plan->work * sb)));
-    void *scratch = nullptr;
-    HIP_TRY(dev_malloc_async(&scratch, per * plan->work * sb, s));
-    for (uint64_t s0 = 0; s0 < n_stripes; s0 += per) {
+    const uint64_t per = fit_stripes(n_stripes, kScratchCap, plan->work * sb);
+    return in_scratch_slices(n_stripes, per, per * plan->work * sb, s, [&](uint64_t s0, uint64_t cnt, uint8_t *scratch) {
       EncodeArgs b = a;
       b.data += s0 * orig_stride;
       b.parity += s0 * rec_stride;
-      b.n_stripes = std::min(per, n_stripes - s0);
-      b.scratch = static_cast<uint8_t *>(scratch);
+      b.n_stripes = cnt;
+      b.scratch = scratch;
       b.scratch_stripes = per;
-      hipError_t e = launch_encode(kc, b, s);
-      if (e != hipSuccess) {
-        (void)hipFreeAsync(scratch, s);
-        return hip_fail(e, "launch_encode");
-      }
-    }
-    HIP_TRY(hipFreeAsync(scratch, s));
-    return RS_OK;
+      return hip_status(launch_encode(kc, b, s), "launch_encode");
+    });
   });
 }
 
@@ -328,21 +321,17 @@ int rs_reconstruct_batch_dev(uint64_t k, uint64_t m, size_t sb, uint64_t n_strip
       }
       // syndrome scratch in slices of <= 4 GiB (slices small enough for the 256 MB Infinity
       // Cache measured slower: less work per launch)
-      const uint64_t cap = 4096ull << 20;
-      const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_stripes, cap / (m * sb)));
-      void *scratch = nullptr;
-      HIP_TRY(dev_malloc_async(&scratch, per * m * sb, s));
-      for (uint64_t s0 = 0; s0 < n_stripes; s0 += per) {
-        const uint64_t cnt = std::min(per, n_stripes - s0);
+      const uint64_t per = fit_stripes(n_stripes, 4096ull << 20, m * sb);
+      return in_scratch_slices(n_stripes, per, per * m * sb, s, [&](uint64_t s0, uint64_t cnt, uint8_t *scratch) {
         EncodeArgs eb = ea;
         eb.data += s0 * orig_stride;
-        eb.parity = static_cast<uint8_t *>(scratch);
+        eb.parity = scratch;
         eb.n_stripes = cnt;
         DecodeArgs db = a;
         db.orig += s0 * orig_stride;
         db.rec += s0 * rec_stride;
         db.out += s0 * out_stride;
-        db.xsrc = static_cast<const uint8_t *>(scratch);
+        db.xsrc = scratch;
         db.xsrc_stripe_stride = m * sb;
         db.n_stripes = cnt;
         hipError_t err = hipSuccess;
@@ -362,13 +351,8 @@ int rs_reconstruct_batch_dev(uint64_t k, uint64_t m, size_t sb, uint64_t n_strip
           else
             err = launch_decode(kc, db, s);
         }
-        if (err != hipSuccess) {
-          (void)hipFreeAsync(scratch, s);
-          return hip_fail(err, "syndrome reconstruct");
-        }
-      }
-      HIP_TRY(hipFreeAsync(scratch, s));
-      return RS_OK;
+        return hip_status(err, "syndrome reconstruct");
+      });
     }
     if (kc.variant != Variant::kGeneric) {
       a.n_stripes = n_stripes;
@@ -378,9 +362,7 @@ int rs_reconstruct_batch_dev(uint64_t k, uint64_t m, size_t sb, uint64_t n_strip
     // launch_decode_generic: the transform plus the FFT's kept rows, per stripe
     const uint64_t rows = decode_generic_rows(plan->work, a.trunc, a.trunc_fft);
     const uint64_t per = slice_stripes(n_stripes, rows * sb);
-    void *scratch = nullptr;
-    HIP_TRY(dev_malloc_async(&scratch, per * rows * sb, s));
-    for (uint64_t s0 = 0; s0 < n_stripes; s0 += per) {
+    return in_scratch_slices(n_stripes, per, per * rows * sb, s, [&](uint64_t s0, uint64_t cnt, uint8_t *scratch) {
       DecodeArgs b = a;
       b.orig += s0 * orig_stride;
       b.rec += s0 * rec_stride;
@@ -389,17 +371,11 @@ int rs_reconstruct_batch_dev(uint64_t k, uint64_t m, size_t sb, uint64_t n_strip
       b.tab_post += s0 * a.pattern_stride;
       b.pos_src += s0 * a.pattern_stride;
       b.pos_dst += s0 * a.pattern_stride;
-      b.n_stripes = std::min(per, n_stripes - s0);
-      b.scratch = static_cast<uint8_t *>(scratch);
+      b.n_stripes = cnt;
+      b.scratch = scratch;
       b.scratch_stripes = per;
-      hipError_t err = launch_decode(kc, b, s);
-      if (err != hipSuccess) {
-        (void)hipFreeAsync(scratch, s);
-        return hip_fail(err, "launch_decode");
-      }
-    }
-    HIP_TRY(hipFreeAsync(scratch, s));
-    return RS_OK;
+      return hip_status(launch_decode(kc, b, s), "launch_decode");
+    });
   });
 }
 

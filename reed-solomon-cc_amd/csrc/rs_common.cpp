@@ -375,8 +375,7 @@ int rs_debug_release_caches(uint64_t *pooled_contexts) {
     release_patterns();
     release_lowrate();
     release_oneshot();
-    release_locate();
-    release_update();
+    release_code_plans();
     release_host_rings();
     {
       std::lock_guard<std::mutex> lk(g_plan_mu);

@@ -1,7 +1,10 @@
 // rs_host.hpp — internal interface of the host codec (librs_amd.so): validation and
 // error reporting, plan caches, kernel selection, plans, and the entry points the
 // C ABI files (rs_batch_dev.cpp, rs_patterns.cpp, rs_lowrate.cpp, rs_host_batch.cpp,
-// rs_oneshot.cpp, rs_verify.cpp, rs_locate.cpp, rs_update.cpp) share. Host-side mirror of root.zig's checks and error
+// rs_oneshot.cpp, rs_verify.cpp, rs_locate.cpp, rs_update.cpp) share: the stream-ordered scratch
+// (StreamScratch, the only place that frees one) and the slice loop over it (in_scratch_slices,
+// sized by rs_slices.hpp), the shard-tail helpers, and the shell of the scrub family (argument
+// front, encode-and-compare step, CodePlan). Host-side mirror of root.zig's checks and error
 // precedence; every device computation runs in the precompiled kernels
 // (rs_kernels.hip, rs_phase_kernels.hip, rs_plan_kernels.hip, rs_locate_kernels.hip, rs_update_kernels.hip) or in a hipRTC kernel (rs_jit / rs_fftnet / rs_psyn); there is no CPU compute path.
 #pragma once
@@ -11,6 +14,7 @@
 #include <atomic>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -28,6 +32,7 @@
 #include "rs_internal.hpp"
 #include "rs_jit.hpp"
 #include "rs_psyn.hpp"
+#include "rs_slices.hpp"
 
 namespace rs {
 namespace host {
@@ -35,6 +40,7 @@ namespace host {
 // ------------------------------------------------------------ errors (rs_common.cpp)
 int fail(int status, const std::string &msg);  // sets rs_last_error()
 int hip_fail(hipError_t e, const char *what);   // hipErrorOutOfMemory -> RS_ERR_OUT_OF_MEMORY
+inline int hip_status(hipError_t e, const char *what) { return e == hipSuccess ? RS_OK : hip_fail(e, what); }
 const char *last_error();
 
 // Allocation-failure injection (rs_debug_fail_alloc; the reference's
@@ -53,8 +59,7 @@ void release_plans();      // rs_plans.cpp (+ twiddles, rs_common.cpp)
 void release_patterns();   // rs_patterns.cpp
 void release_lowrate();    // rs_lowrate.cpp
 void release_oneshot();    // rs_oneshot.cpp
-void release_locate();     // rs_locate.cpp
-void release_update();     // rs_update.cpp
+void release_code_plans(); // rs_verify.cpp: the locate and update plans
 size_t oneshot_pooled();   // one-shot contexts idle in the pool
 void release_host_rings(); // rs_host_batch.cpp
 
@@ -239,16 +244,47 @@ int upload(const void *host, size_t bytes, int dev, std::shared_ptr<DevBuf> &out
 // HBM for the life of the process; *off_fft = byte offset of the FFT tables
 int twiddle_plan(int dev, uint64_t W, uint32_t flags, std::shared_ptr<DevBuf> &out, size_t &off_fft);
 
-constexpr uint64_t kScratchCap = 2ull << 30;  // generic path: scratch per launch
-static_assert(env::kTable[env::SCRATCH_CAP_MB].def == kScratchCap >> 20, "the knob's default is kScratchCap");
-// the generic kernels' scratch cap per launch: kScratchCap, or RS_AMD_SCRATCH_CAP_MB
-inline uint64_t scratch_cap() { return static_cast<uint64_t>(env::num(env::SCRATCH_CAP_MB)) << 20; }
-// stripes per scratch slice: as many as fit the cap, spread evenly over the slices (a short
-// last slice runs its launches at lower occupancy)
-inline uint64_t slice_stripes(uint64_t n, uint64_t per_stripe_bytes) {
-  const uint64_t fit = std::max<uint64_t>(1, std::min<uint64_t>(n, scratch_cap() / per_stripe_bytes));
-  const uint64_t slices = (n + fit - 1) / fit;
-  return (n + slices - 1) / slices;
+// ------------------------------------------------------- stream-ordered scratch
+// One stream-ordered allocation, freed on its stream on every exit path.
+class StreamScratch {
+ public:
+  StreamScratch() = default;
+  StreamScratch(StreamScratch &&o) noexcept : p_(o.p_), s_(o.s_) { o.p_ = nullptr; }
+  StreamScratch(const StreamScratch &) = delete;
+  StreamScratch &operator=(const StreamScratch &) = delete;
+  StreamScratch &operator=(StreamScratch &&) = delete;
+  // the free's status is ignored: a failing free of a live pool pointer cannot be shown to
+  // occur, and a failed stream reports itself at the caller's next call on it
+  ~StreamScratch() {
+    if (p_) (void)hipFreeAsync(p_, s_);
+  }
+  // one counted allocation (dev_malloc_async); an OOM maps to RS_ERR_OUT_OF_MEMORY
+  int alloc(size_t bytes, hipStream_t s) {
+    s_ = s;
+    const hipError_t e = dev_malloc_async(&p_, bytes, s);
+    return e == hipSuccess ? RS_OK : hip_fail(e, "dev_malloc_async");
+  }
+  uint8_t *bytes() const { return static_cast<uint8_t *>(p_); }
+  template <class T>
+  T *at(size_t off = 0) const {
+    return reinterpret_cast<T *>(bytes() + off);
+  }
+
+ private:
+  void *p_ = nullptr;
+  hipStream_t s_ = nullptr;
+};
+
+// n stripes in slices of `per` over one scratch of `bytes` bytes: body(s0, cnt, scratch) runs
+// on stripes [s0, s0 + cnt), cnt <= per, and returns a status; the first that is not RS_OK
+// ends the walk. `per` comes from slice_stripes or fit_stripes (rs_slices.hpp).
+template <class F>
+int in_scratch_slices(uint64_t n, uint64_t per, size_t bytes, hipStream_t s, F &&body) {
+  StreamScratch scratch;
+  if (int st = scratch.alloc(bytes, s)) return st;
+  for (uint64_t s0 = 0; s0 < n; s0 += per)
+    if (int st = body(s0, std::min(per, n - s0), scratch.bytes())) return st;
+  return RS_OK;
 }
 
 // ------------------------------------------------- kernel selection (rs_select.cpp)
@@ -282,9 +318,56 @@ int get_decode_plan(int dev, uint64_t k, uint64_t m, uint64_t sb, uint32_t flags
 // in slices of <= kTailSliceBytes.
 constexpr uint64_t kTailSliceBytes = 1ull << 30;
 int pad_shards(const uint8_t *src, uint64_t src_stripe_stride, uint64_t sb, uint8_t *dst, uint64_t dst_stripe_stride,
-               uint64_t psb, uint64_t n, hipStream_t s);
+               uint64_t n, hipStream_t s);
 int unpad_shards(const uint8_t *src, uint64_t src_stripe_stride, uint64_t sb, uint8_t *dst, uint64_t dst_stripe_stride,
                  uint64_t n, hipStream_t s);
+// a group of `rows` shards per stripe: src rows of sb bytes -> the padded block dst
+// ([stripe][rows][psb]); with `present`, only the rows it marks
+int pad_group(const uint8_t *src, uint64_t src_stripe_stride, uint64_t sb, uint64_t rows, const uint8_t *present,
+              uint8_t *dst, uint64_t psb, uint64_t n, hipStream_t s);
+// the other way: the padded block src -> dst rows of sb bytes
+int unpad_group(const uint8_t *src, uint64_t psb, uint64_t rows, uint8_t *dst, uint64_t dst_stripe_stride, uint64_t sb,
+                uint64_t n, hipStream_t s);
+// rs_reconstruct_batch_dev_patterns on shards with a tail: all k + m + max_e rows padded
+int patterns_tail(uint64_t k, uint64_t m, uint64_t sb, uint64_t n, const uint8_t *d_present, uint64_t present_stride,
+                  uint32_t max_e, const uint8_t *orig, uint64_t ostride, const uint8_t *rec, uint64_t rstride,
+                  uint8_t *out, uint64_t outstride, int32_t *d_status, uint32_t flags, hipStream_t s);
+
+// ------------------------------- the scrub family: verify, locate, update (rs_verify.cpp)
+// The argument front of verify and locate, in this order: k == 0, check_codec, a NULL among
+// the three pointers, stride defaulting, "stripe stride too small". An empty batch (n == 0)
+// passes once the codec is valid; the caller then returns RS_OK.
+int check_scrub_args(uint64_t k, uint64_t m, size_t sb, uint64_t n, const void *d_original, uint64_t *orig_stride,
+                     const void *d_recovery, uint64_t *rec_stride, const void *third);
+// one slice: rs_encode_batch_dev of `cnt` stripes into `scratch` ([stripe][m][sb]), then
+// launch_verify_compare of it with the stored shards into the flag rows `bad`
+int encode_and_compare(uint64_t k, uint64_t m, uint64_t sb, uint64_t cnt, const uint8_t *orig, uint64_t ostride,
+                       uint8_t *scratch, const uint8_t *rec, uint64_t rstride, uint8_t *bad, uint64_t bad_stride,
+                       uint32_t flags, hipStream_t s);
+// Per (device, k, m): one blob of uint16 in HBM (locate: ratio logs; update: coefficient logs)
+struct CodePlan {
+  std::shared_ptr<DevBuf> buf;
+  const uint16_t *u16() const { return static_cast<const uint16_t *>(buf->p); }
+};
+extern PlanCache<CodePlan> g_locate_plans, g_update_plans;
+// the cached plan, or build(blob) uploaded; build fails with its own message (fail())
+int get_code_plan(PlanCache<CodePlan> &cache, int dev, uint64_t k, uint64_t m,
+                  const std::function<int(std::vector<uint16_t> &)> &build, std::shared_ptr<CodePlan> &out);
+
+// the selftests' random stream (splitmix64)
+struct SplitMix64 {
+  uint64_t state;
+  explicit SplitMix64(uint64_t seed) : state(seed * 0x9E3779B97F4A7C15ull + 1) {}
+  uint64_t operator()() {
+    uint64_t z = (state += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+  }
+};
+// the scalar encode column by column: d [k][P] symbols -> p [m][P]; hr = use_high_rate(k, m)
+void encode_columns(int hr, uint64_t k, uint64_t m, uint64_t P, const std::vector<uint16_t> &d,
+                    std::vector<uint16_t> &p);
 
 // ---------------------------------------------------------- low rate (rs_lowrate.cpp)
 int low_encode(int dev, uint64_t k, uint64_t m, uint64_t sb, uint64_t n, const uint8_t *orig, uint64_t ostride,

@@ -34,29 +34,15 @@ bool ratio_logs(uint64_t k, uint64_t m, std::vector<uint16_t> &dl) {
 
 // Per (device, k, m): rlog [k] (the row-1 ratio logs, contiguous for the candidate match), then
 // dl [k][m - 1]
-struct LocatePlan {
-  std::shared_ptr<DevBuf> buf;
-  const uint16_t *rlog() const { return static_cast<const uint16_t *>(buf->p); }
-};
-PlanCache<LocatePlan> g_locate_plans;
-
-int get_locate_plan(int dev, uint64_t k, uint64_t m, std::shared_ptr<LocatePlan> &out) {
-  const std::string key = std::to_string(dev) + "/" + std::to_string(k) + "/" + std::to_string(m);
-  {
-    std::lock_guard<std::mutex> lk(g_plan_mu);
-    if ((out = g_locate_plans.find(key))) return RS_OK;
-  }
-  alloc_point();
-  auto p = std::make_shared<LocatePlan>();
-  std::vector<uint16_t> dl;
-  if (!ratio_logs(k, m, dl)) return fail(RS_ERR_DEVICE, "locate: the code's coefficient ratios are not distinct");
-  std::vector<uint16_t> blob(k + dl.size());
-  for (uint64_t j = 0; j < k; j++) blob[j] = dl[j * (m - 1)];
-  std::copy(dl.begin(), dl.end(), blob.begin() + k);
-  if (int st = upload(blob.data(), blob.size() * sizeof(uint16_t), dev, p->buf)) return st;
-  std::lock_guard<std::mutex> lk(g_plan_mu);
-  out = g_locate_plans.insert(key, p);
-  return RS_OK;
+int get_locate_plan(int dev, uint64_t k, uint64_t m, std::shared_ptr<CodePlan> &out) {
+  return get_code_plan(g_locate_plans, dev, k, m, [&](std::vector<uint16_t> &blob) -> int {
+    std::vector<uint16_t> dl;
+    if (!ratio_logs(k, m, dl)) return fail(RS_ERR_DEVICE, "locate: the code's coefficient ratios are not distinct");
+    blob.resize(k + dl.size());
+    for (uint64_t j = 0; j < k; j++) blob[j] = dl[j * (m - 1)];
+    std::copy(dl.begin(), dl.end(), blob.begin() + k);
+    return RS_OK;
+  }, out);
 }
 
 // The scratch of one slice: the encode, then per stripe the candidate's tables, its class, the
@@ -77,39 +63,30 @@ struct Scratch {
 int locate_slices(int dev, uint64_t k, uint64_t m, uint64_t sb, uint64_t n, const uint8_t *orig, uint64_t ostride,
                   const uint8_t *rec, uint64_t rstride, int32_t *located, uint8_t *present, uint64_t pstride,
                   uint64_t *counts, hipStream_t s) {
-  std::shared_ptr<LocatePlan> plan;
+  std::shared_ptr<CodePlan> plan;
   const uint16_t *dexp = nullptr, *dlog = nullptr, *dlw = nullptr;
   int st;
   if (m >= 2) {  // m == 1 has no ratio: a disagreeing stripe is unlocated
     if ((st = get_locate_plan(dev, k, m, plan))) return st;
     if ((st = device_tables(dev, &dexp, &dlog, &dlw))) return st;
   }
+  const uint16_t *rlog = plan ? plan->u16() : nullptr;  // then dl at rlog + k
   const Scratch L(n, m, sb);
-  void *mem = nullptr;
-  HIP_TRY(dev_malloc_async(&mem, L.bytes, s));
-  uint8_t *base = static_cast<uint8_t *>(mem);
-  RsTab *tabs = reinterpret_cast<RsTab *>(base + L.tabs);
-  int32_t *cls = reinterpret_cast<int32_t *>(base + L.cls);
-  uint8_t *bad = base + L.bad, *reject = base + L.reject;
   const uint32_t k32 = static_cast<uint32_t>(k), m32 = static_cast<uint32_t>(m);
-  hipError_t e = counts ? hipMemsetAsync(counts, 0, 4 * sizeof(uint64_t), s) : hipSuccess;
-  if (e != hipSuccess) st = hip_fail(e, "hipMemsetAsync(d_counts)");
-  for (uint64_t s0 = 0; st == RS_OK && s0 < n; s0 += L.per) {
-    const uint64_t cnt = std::min(L.per, n - s0);
+  return in_scratch_slices(n, L.per, L.bytes, s, [&](uint64_t s0, uint64_t cnt, uint8_t *base) {
+    RsTab *tabs = reinterpret_cast<RsTab *>(base + L.tabs);
+    int32_t *cls = reinterpret_cast<int32_t *>(base + L.cls);
+    uint8_t *bad = base + L.bad, *reject = base + L.reject;
+    if (s0 == 0 && counts)
+      if (int st = hip_status(hipMemsetAsync(counts, 0, 4 * sizeof(uint64_t), s), "hipMemsetAsync(d_counts)")) return st;
     const uint8_t *rec0 = rec + s0 * rstride;
     // the compare and the confirm only ever store 1: flags and reject bytes start at 0
-    if ((e = hipMemsetAsync(bad, 0, L.per * (m + 1), s)) != hipSuccess) {
-      st = hip_fail(e, "hipMemsetAsync(flags)");
-      break;
-    }
-    if ((st = rs_encode_batch_dev(k, m, sb, cnt, orig + s0 * ostride, ostride, base, 0, 0, s))) break;
-    const char *what = "launch_verify_compare";
-    e = launch_verify_compare(base, m * sb, rec0, rstride, sb, cnt, m32, bad, m, s);
-    if (e == hipSuccess) {
-      what = "launch_locate_classify";
-      e = launch_locate_classify(base, m * sb, rec0, rstride, sb, cnt, k32, m32, bad, plan ? plan->rlog() : nullptr,
-                                 plan ? plan->rlog() + k : nullptr, dexp, dlog, tabs, cls, s);
-    }
+    if (int st = hip_status(hipMemsetAsync(bad, 0, L.per * (m + 1), s), "hipMemsetAsync(flags)")) return st;
+    if (int st = encode_and_compare(k, m, sb, cnt, orig + s0 * ostride, ostride, base, rec0, rstride, bad, m, 0, s))
+      return st;
+    const char *what = "launch_locate_classify";
+    hipError_t e = launch_locate_classify(base, m * sb, rec0, rstride, sb, cnt, k32, m32, bad, rlog,
+                                          rlog ? rlog + k : nullptr, dexp, dlog, tabs, cls, s);
     if (e == hipSuccess) {
       what = "launch_locate_confirm";
       e = launch_locate_confirm(base, m * sb, rec0, rstride, sb, cnt, k32, m32, cls, tabs, reject, s);
@@ -119,10 +96,8 @@ int locate_slices(int dev, uint64_t k, uint64_t m, uint64_t sb, uint64_t n, cons
       e = launch_locate_finish(cls, bad, reject, k32, m32, cnt, located + s0, present ? present + s0 * pstride : nullptr,
                                pstride, counts, s);
     }
-    if (e != hipSuccess) st = hip_fail(e, what);
-  }
-  (void)hipFreeAsync(mem, s);
-  return st;
+    return hip_status(e, what);
+  });
 }
 
 // ---- the same algorithm on the host, P symbols per shard (rs_locate_selftest): S [m][P]
@@ -152,11 +127,6 @@ int64_t locate_scalar(uint64_t k, uint64_t m, uint64_t P, const uint16_t *S, con
 
 }  // namespace
 
-void release_locate() {
-  std::lock_guard<std::mutex> lk(g_plan_mu);
-  g_locate_plans.clear();
-}
-
 }  // namespace host
 }  // namespace rs
 
@@ -171,15 +141,9 @@ int rs_locate_batch_dev(uint64_t k, uint64_t m, size_t sb, uint64_t n_stripes, c
                         rs_stream_t stream) {
   TraceScope ts;
   return guarded([&]() -> int {
-    if (k == 0) return fail(RS_ERR_TOO_FEW_ORIGINAL_SHARDS, "original_count == 0");
-    int st = check_codec(k, m, sb);
-    if (st) return st;
-    if (n_stripes == 0) return RS_OK;
-    if (!d_original || !d_recovery || !d_located) return fail(RS_ERR_INVALID_ARGUMENT, "NULL device pointer");
-    if (orig_stride == 0) orig_stride = k * sb;
-    if (rec_stride == 0) rec_stride = m * sb;
+    int st = check_scrub_args(k, m, sb, n_stripes, d_original, &orig_stride, d_recovery, &rec_stride, d_located);
+    if (st || n_stripes == 0) return st;
     if (present_stride == 0) present_stride = k + m;
-    if (orig_stride < k * sb || rec_stride < m * sb) return fail(RS_ERR_INVALID_ARGUMENT, "stripe stride too small");
     if (present_stride < k + m) return fail(RS_ERR_INVALID_ARGUMENT, "present_stride below the shard count");
     // the syndrome ratios need a linear encode that reads every original
     if (flags != 0) return fail(RS_ERR_INVALID_ARGUMENT, "locate needs the corrected arithmetic (flags == 0)");
@@ -204,26 +168,12 @@ int rs_locate_selftest(uint64_t k, uint64_t m, int trials, uint64_t seed, uint64
     if (k == 0) return fail(RS_ERR_INVALID_ARGUMENT, "original_count == 0");
     const int hr = use_high_rate(k, m);
     if (hr < 0) return fail(-hr, "unsupported shard count (root.zig:397-415)");
-    uint64_t state = seed * 0x9E3779B97F4A7C15ull + 1;
-    auto rnd = [&]() {  // splitmix64
-      uint64_t z = (state += 0x9E3779B97F4A7C15ull);
-      z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-      z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-      return z ^ (z >> 31);
-    };
+    SplitMix64 rnd(seed);
     uint64_t bad = 0;
     std::vector<uint16_t> dl;
     if (m >= 2 && !ratio_logs(k, m, dl)) bad++;  // a zero coefficient or a repeated ratio
     constexpr uint64_t P = 4;  // symbols per shard
-    std::vector<uint16_t> data(k * P), par(m * P), S(m * P), col(k), out(m);
-    auto encode = [&](const std::vector<uint16_t> &d, std::vector<uint16_t> &p) {
-      for (uint64_t q = 0; q < P; q++) {
-        for (uint64_t j = 0; j < k; j++) col[j] = d[j * P + q];
-        if (hr == 0) scalar_encode_low(col.data(), k, m, false, out.data());
-        else scalar_encode(col.data(), k, m, false, false, out.data());
-        for (uint64_t r = 0; r < m; r++) p[r * P + q] = out[r];
-      }
-    };
+    std::vector<uint16_t> data(k * P), par(m * P), S(m * P);
     // a nonzero error at symbol q0 of the shard at x, and with probability 1/2 at each other symbol
     auto corrupt = [&](uint16_t *x) {
       const uint64_t q0 = rnd() % P;
@@ -232,7 +182,7 @@ int rs_locate_selftest(uint64_t k, uint64_t m, int trials, uint64_t seed, uint64
     };
     for (int t = 0; bad == 0 && t < trials; t++) {
       for (auto &x : data) x = static_cast<uint16_t>(rnd());
-      encode(data, par);
+      encode_columns(hr, k, m, P, data, par);
       for (int mode = 0; mode < 5; mode++) {
         std::vector<uint16_t> d2 = data, stored = par;
         int64_t want = RS_LOCATE_CLEAN;
@@ -258,7 +208,7 @@ int rs_locate_selftest(uint64_t k, uint64_t m, int trials, uint64_t seed, uint64
           corrupt(&stored[b * P]);
           want = RS_LOCATE_RECOVERY_SET;
         }
-        encode(d2, S);
+        encode_columns(hr, k, m, P, d2, S);
         for (uint64_t i = 0; i < m * P; i++) S[i] ^= stored[i];
         const int64_t got = locate_scalar(k, m, P, S.data(), dl);
         if (any_but_single ? got >= 0 : got != want) bad++;

@@ -350,17 +350,13 @@ int get_low_decode_plan(int dev, uint64_t k, uint64_t m, uint64_t sb, const uint
   return RS_OK;
 }
 
-// generic kernels walk a scratch of `per_stripe` positions x sb per stripe, in slices
+// generic kernels walk a scratch of `per_stripe_bytes` per stripe, in balanced slices
 template <class F>
-int in_scratch_slices(uint64_t n, uint64_t per_stripe_bytes, hipStream_t s, F &&launch) {
+int low_slices(uint64_t n, uint64_t per_stripe_bytes, hipStream_t s, F &&launch) {
   const uint64_t per = slice_stripes(n, per_stripe_bytes);
-  void *scratch = nullptr;
-  HIP_TRY(dev_malloc_async(&scratch, per * per_stripe_bytes, s));
-  hipError_t e = hipSuccess;
-  for (uint64_t s0 = 0; e == hipSuccess && s0 < n; s0 += per)
-    e = launch(s0, std::min(per, n - s0), static_cast<uint8_t *>(scratch));
-  (void)hipFreeAsync(scratch, s);
-  return e == hipSuccess ? RS_OK : hip_fail(e, "low-rate generic kernel");
+  return in_scratch_slices(n, per, per * per_stripe_bytes, s, [&](uint64_t s0, uint64_t cnt, uint8_t *scratch) {
+    return hip_status(launch(s0, cnt, scratch), "low-rate generic kernel");
+  });
 }
 
 }  // namespace
@@ -401,7 +397,7 @@ int low_encode(int dev, uint64_t k, uint64_t m, uint64_t sb, uint64_t n, const u
   const uint64_t fit = scratch_cap() / region;  // regions of one stripe that fit the cap
   const uint64_t G = std::max<uint64_t>(1, std::min<uint64_t>(p->n_chunks, fit > 1 ? fit - 1 : 1));
   a.regions = static_cast<uint32_t>(1 + G);
-  return in_scratch_slices(n, (1 + G) * region, s, [&](uint64_t s0, uint64_t cnt, uint8_t *scratch) {
+  return low_slices(n, (1 + G) * region, s, [&](uint64_t s0, uint64_t cnt, uint8_t *scratch) {
     EncodeArgs b = a;
     b.data += s0 * ostride;
     b.parity += s0 * rstride;
@@ -455,7 +451,7 @@ int low_reconstruct(int dev, uint64_t k, uint64_t m, uint64_t sb, uint64_t n, co
     L.gamma1 = reinterpret_cast<const RsTab *>(base + p->off_gamma1);
     L.u = p->u.data();
     L.used = p->used.data();
-    return in_scratch_slices(n, low_block_rows(p->C, k) * sb, s, [&](uint64_t s0, uint64_t cnt, uint8_t *scratch) {
+    return low_slices(n, low_block_rows(p->C, k) * sb, s, [&](uint64_t s0, uint64_t cnt, uint8_t *scratch) {
       LowBlockArgs b = L;
       b.enc.data += s0 * ostride;
       b.rec += s0 * rstride;
@@ -491,7 +487,7 @@ int low_reconstruct(int dev, uint64_t k, uint64_t m, uint64_t sb, uint64_t n, co
     HIP_TRY(launch_decode(kc, a, s));
     return RS_OK;
   }
-  return in_scratch_slices(n, decode_generic_rows(p->W, p->trunc, k) * sb, s, [&](uint64_t s0, uint64_t cnt, uint8_t *scratch) {
+  return low_slices(n, decode_generic_rows(p->W, p->trunc, k) * sb, s, [&](uint64_t s0, uint64_t cnt, uint8_t *scratch) {
     DecodeArgs b = a;
     b.orig += s0 * ostride;
     b.rec += s0 * rstride;
@@ -638,13 +634,7 @@ extern "C" int rs_lowrate_selftest(uint64_t k, uint64_t m, int trials, uint64_t 
     if (hr < 0) return fail(-hr, "unsupported shard count (root.zig:397-415)");
     if (hr == 1) return fail(RS_ERR_INVALID_ARGUMENT, "not a low-rate code");
     const uint64_t C = ceil_pow2(k), W = ceil_pow2(C + m);
-    uint64_t state = seed * 0x9E3779B97F4A7C15ull + 1;
-    auto rnd = [&]() {  // splitmix64
-      uint64_t z = (state += 0x9E3779B97F4A7C15ull);
-      z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-      z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-      return z ^ (z >> 31);
-    };
+    SplitMix64 rnd(seed);
     uint64_t bad = 0;
     std::vector<uint16_t> data(k), par(m), sym(W), er(kOrder);
     std::vector<uint8_t> present(k + m), received(W);

@@ -232,6 +232,27 @@ void rs::host::release_patterns() {
   g_psyn_plans.clear();
 }
 
+// Every slot is padded (which are present varies per stripe; the kernels read only those), and
+// the restored rows too, so the slots a stripe does not restore come back unchanged.
+int rs::host::patterns_tail(uint64_t k, uint64_t m, uint64_t sb, uint64_t n, const uint8_t *d_present,
+                            uint64_t present_stride, uint32_t max_e, const uint8_t *orig, uint64_t ostride,
+                            const uint8_t *rec, uint64_t rstride, uint8_t *out, uint64_t outstride, int32_t *d_status,
+                            uint32_t flags, hipStream_t s) {
+  const uint64_t psb = (sb + 63) / 64 * 64, rows = k + m + max_e;
+  const uint64_t cap = fit_stripes(n, kTailSliceBytes, rows * psb);
+  return in_scratch_slices(n, cap, cap * rows * psb, s, [&](uint64_t s0, uint64_t cnt, uint8_t *po) {
+    uint8_t *pr = po + cap * k * psb, *pout = pr + cap * m * psb;
+    int st = pad_group(orig + s0 * ostride, ostride, sb, k, nullptr, po, psb, cnt, s);
+    if (st == RS_OK) st = pad_group(rec + s0 * rstride, rstride, sb, m, nullptr, pr, psb, cnt, s);
+    if (st == RS_OK) st = pad_group(out + s0 * outstride, outstride, sb, max_e, nullptr, pout, psb, cnt, s);
+    if (st == RS_OK)
+      st = rs_reconstruct_batch_dev_patterns(k, m, psb, cnt, d_present + s0 * present_stride, present_stride, max_e, po,
+                                             0, pr, 0, pout, 0, d_status ? d_status + s0 : nullptr, flags, s);
+    if (st == RS_OK) st = unpad_group(pout, psb, max_e, out + s0 * outstride, outstride, sb, cnt, s);
+    return st;
+  });
+}
+
 extern "C" {
 
 const char *rs_patterns_kernel_name(uint64_t k, uint64_t m, size_t sb, uint32_t max_e, uint32_t flags) {
@@ -272,34 +293,10 @@ int rs_reconstruct_batch_dev_patterns(uint64_t k, uint64_t m, size_t sb, uint64_
     if (sb % 64) {  // shard tails (root.zig:338-348 layout): padded copies, in slices
       int dev;
       if ((st = current_device(&dev))) return st;
-      hipStream_t s = static_cast<hipStream_t>(stream);
-      const uint64_t psb = (sb + 63) / 64 * 64, rows = k + m + max_e;
-      const uint64_t cap = std::max<uint64_t>(1, std::min<uint64_t>(n_stripes, kTailSliceBytes / (rows * psb)));
-      void *buf = nullptr;
-      HIP_TRY(dev_malloc_async(&buf, cap * rows * psb, s));
-      uint8_t *po = static_cast<uint8_t *>(buf), *pr = po + cap * k * psb, *pout = pr + cap * m * psb;
-      const uint8_t *O = static_cast<const uint8_t *>(d_original), *Rc = static_cast<const uint8_t *>(d_recovery);
-      uint8_t *Out = static_cast<uint8_t *>(d_restored);
-      for (uint64_t s0 = 0; st == RS_OK && s0 < n_stripes; s0 += cap) {
-        const uint64_t cnt = std::min(cap, n_stripes - s0);
-        // every slot is padded (which are present varies per stripe; the kernels read only
-        // those), and the restored rows too, so the slots a stripe does not restore come
-        // back unchanged
-        for (uint64_t i = 0; st == RS_OK && i < k; i++)
-          st = pad_shards(O + s0 * orig_stride + i * sb, orig_stride, sb, po + i * psb, k * psb, psb, cnt, s);
-        for (uint64_t i = 0; st == RS_OK && i < m; i++)
-          st = pad_shards(Rc + s0 * rec_stride + i * sb, rec_stride, sb, pr + i * psb, m * psb, psb, cnt, s);
-        for (uint64_t j = 0; st == RS_OK && j < max_e; j++)
-          st = pad_shards(Out + s0 * out_stride + j * sb, out_stride, sb, pout + j * psb, max_e * psb, psb, cnt, s);
-        if (st == RS_OK)
-          st = rs_reconstruct_batch_dev_patterns(k, m, psb, cnt, d_present + s0 * present_stride, present_stride, max_e,
-                                                 po, 0, pr, 0, pout, 0, d_status ? d_status + s0 : nullptr, flags,
-                                                 stream);
-        for (uint64_t j = 0; st == RS_OK && j < max_e; j++)
-          st = unpad_shards(pout + j * psb, max_e * psb, sb, Out + s0 * out_stride + j * sb, out_stride, cnt, s);
-      }
-      (void)hipFreeAsync(buf, s);
-      return st;
+      return patterns_tail(k, m, sb, n_stripes, d_present, present_stride, max_e,
+                           static_cast<const uint8_t *>(d_original), orig_stride,
+                           static_cast<const uint8_t *>(d_recovery), rec_stride, static_cast<uint8_t *>(d_restored),
+                           out_stride, d_status, flags, static_cast<hipStream_t>(stream));
     }
     const int max_nv = align_nv({reinterpret_cast<uint64_t>(d_original), reinterpret_cast<uint64_t>(d_recovery),
                                  reinterpret_cast<uint64_t>(d_restored), orig_stride, rec_stride, out_stride});
@@ -319,18 +316,16 @@ int rs_reconstruct_batch_dev_patterns(uint64_t k, uint64_t m, size_t sb, uint64_
         hipStream_t s = static_cast<hipStream_t>(stream);
         const uint32_t mo = psyn::max_out(static_cast<uint32_t>(k), static_cast<uint32_t>(m));
         const uint32_t pdw = psyn::plan_dwords(static_cast<uint32_t>(k), static_cast<uint32_t>(m));
-        void *blk = nullptr;
-        HIP_TRY(dev_malloc_async(&blk, n_stripes * pdw * sizeof(uint32_t), s));
+        StreamScratch blk;
+        if ((st = blk.alloc(n_stripes * pdw * sizeof(uint32_t), s))) return st;
         hipError_t e = launch_psyn_plan(d_present, present_stride, static_cast<uint32_t>(k), static_cast<uint32_t>(m), mo,
                                         max_e, n_stripes, static_cast<const uint16_t *>(pp->G->p), dexp, dlog,
-                                        static_cast<uint32_t *>(blk), pdw, d_status, s);
+                                        blk.at<uint32_t>(), pdw, d_status, s);
         if (e == hipSuccess)
           e = psyn::launch(*pk, pp->spec, static_cast<const uint8_t *>(d_original), orig_stride,
                            static_cast<const uint8_t *>(d_recovery), rec_stride, static_cast<uint8_t *>(d_restored),
-                           out_stride, sb, n_stripes, static_cast<const uint32_t *>(blk), s);
-        (void)hipFreeAsync(blk, s);
-        if (e != hipSuccess) return hip_fail(e, "per-stripe syndrome network");
-        return RS_OK;
+                           out_stride, sb, n_stripes, blk.at<uint32_t>(), s);
+        return hip_status(e, "per-stripe syndrome network");
       }
     }
     // wide codes: the fused FFT reconstruct with per-stripe decode blocks built on the GPU
@@ -354,27 +349,21 @@ int rs_reconstruct_batch_dev_patterns(uint64_t k, uint64_t m, size_t sb, uint64_
         fftnet::uv_basis(cst.p);
         // decode blocks in slices of <= 1 GiB
         const uint64_t per_bytes = static_cast<uint64_t>(words) * 4 + (k + m) + W * 2;
-        const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_stripes, (1ull << 30) / per_bytes));
-        void *tmp = nullptr;
-        HIP_TRY(dev_malloc_async(&tmp, per * per_bytes + 256, s));
-        uint32_t *blk = static_cast<uint32_t *>(tmp);
-        uint16_t *logs = reinterpret_cast<uint16_t *>(blk + per * words);
-        uint8_t *trimmed = reinterpret_cast<uint8_t *>(logs + per * W);
-        hipError_t e = hipSuccess;
-        for (uint64_t s0 = 0; e == hipSuccess && s0 < n_stripes; s0 += per) {
-          const uint64_t cnt = std::min(per, n_stripes - s0);
-          e = launch_fdec_plan(d_present + s0 * present_stride, present_stride, static_cast<uint32_t>(k),
-                               static_cast<uint32_t>(m), static_cast<uint32_t>(C), static_cast<uint32_t>(W), cnt, max_e,
-                               dexp, dlog, dlw, trimmed, logs, blk, dwm, mko, words, cst,
-                               d_status ? d_status + s0 : nullptr, s);
+        const uint64_t per = fit_stripes(n_stripes, 1ull << 30, per_bytes);
+        return in_scratch_slices(n_stripes, per, per * per_bytes + 256, s, [&](uint64_t s0, uint64_t cnt, uint8_t *tmp) {
+          uint32_t *blk = reinterpret_cast<uint32_t *>(tmp);
+          uint16_t *logs = reinterpret_cast<uint16_t *>(blk + per * words);
+          uint8_t *trimmed = reinterpret_cast<uint8_t *>(logs + per * W);
+          hipError_t e = launch_fdec_plan(d_present + s0 * present_stride, present_stride, static_cast<uint32_t>(k),
+                                          static_cast<uint32_t>(m), static_cast<uint32_t>(C), static_cast<uint32_t>(W),
+                                          cnt, max_e, dexp, dlog, dlw, trimmed, logs, blk, dwm, mko, words, cst,
+                                          d_status ? d_status + s0 : nullptr, s);
           if (e == hipSuccess)
             e = fftnet::launch(*fk, *dfs, static_cast<const uint8_t *>(d_original) + s0 * orig_stride, orig_stride,
                                static_cast<const uint8_t *>(d_recovery) + s0 * rec_stride, rec_stride,
                                static_cast<uint8_t *>(d_restored) + s0 * out_stride, out_stride, sb, cnt, s, blk, words);
-        }
-        (void)hipFreeAsync(tmp, s);
-        if (e != hipSuccess) return hip_fail(e, "per-stripe fused FFT reconstruct");
-        return RS_OK;
+          return hip_status(e, "per-stripe fused FFT reconstruct");
+        });
       }
       if (fdec_mode() == 1) return fail(RS_ERR_DEVICE, "RS_AMD_FDEC=1: fused FFT reconstruct kernel unavailable");
     }
@@ -392,29 +381,27 @@ int rs_reconstruct_batch_dev_patterns(uint64_t k, uint64_t m, size_t sb, uint64_
         // coefficients for min(max_e, m) outputs per syndrome, in groups of 8
         const uint32_t cs = wps_coef_stride(static_cast<uint32_t>(std::min<uint64_t>(max_e, m)));
         const uint32_t dmw = fftnet::dyn_mask_words(*fs), pw = dmw + 2 + 64 + 64 * cs;
-        const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_stripes, kScratchCap / (m * sb)));
-        void *blk = nullptr, *scratch = nullptr;
-        HIP_TRY(dev_malloc_async(&blk, n_stripes * pw * sizeof(uint32_t), s));
-        hipError_t e = dev_malloc_async(&scratch, per * m * sb, s);
-        if (e == hipSuccess)
-          e = launch_wps_plan(d_present, present_stride, static_cast<uint32_t>(k), static_cast<uint32_t>(m),
-                              static_cast<uint32_t>(std::min<uint64_t>(max_e, m)), n_stripes, static_cast<const uint16_t *>(pp->G->p), dexp, dlog, static_cast<uint32_t *>(blk),
-                              pw, dmw, d_status, s);
+        const uint64_t per = fit_stripes(n_stripes, kScratchCap, m * sb);
+        // two buffers, and the plan kernel runs between the second allocation and the first
+        // slice: the loop is written out here
+        StreamScratch blk, scratch;
+        if ((st = blk.alloc(n_stripes * pw * sizeof(uint32_t), s))) return st;
+        if ((st = scratch.alloc(per * m * sb, s))) return st;
+        hipError_t e = launch_wps_plan(d_present, present_stride, static_cast<uint32_t>(k), static_cast<uint32_t>(m),
+                                       static_cast<uint32_t>(std::min<uint64_t>(max_e, m)), n_stripes,
+                                       static_cast<const uint16_t *>(pp->G->p), dexp, dlog, blk.at<uint32_t>(), pw, dmw,
+                                       d_status, s);
         for (uint64_t s0 = 0; e == hipSuccess && s0 < n_stripes; s0 += per) {
           const uint64_t cnt = std::min(per, n_stripes - s0);
-          const uint32_t *bl = static_cast<const uint32_t *>(blk) + s0 * pw;
+          const uint32_t *bl = blk.at<uint32_t>() + s0 * pw;
           e = fftnet::launch(*fk, *fs, static_cast<const uint8_t *>(d_original) + s0 * orig_stride, orig_stride, nullptr,
-                             0, static_cast<uint8_t *>(scratch), m * sb, sb, cnt, s, bl, pw);
+                             0, scratch.bytes(), m * sb, sb, cnt, s, bl, pw);
           if (e == hipSuccess)
             e = psyn::launch_solve(*sk, static_cast<const uint8_t *>(d_recovery) + s0 * rec_stride, rec_stride,
-                                   static_cast<const uint8_t *>(scratch), m * sb,
-                                   static_cast<uint8_t *>(d_restored) + s0 * out_stride, out_stride, sb, cnt, bl, pw,
-                                   dmw, cs, s);
+                                   scratch.bytes(), m * sb, static_cast<uint8_t *>(d_restored) + s0 * out_stride,
+                                   out_stride, sb, cnt, bl, pw, dmw, cs, s);
         }
-        if (scratch) (void)hipFreeAsync(scratch, s);
-        (void)hipFreeAsync(blk, s);
-        if (e != hipSuccess) return hip_fail(e, "per-stripe wide-code reconstruct");
-        return RS_OK;
+        return hip_status(e, "per-stripe wide-code reconstruct");
       }
     }
     std::shared_ptr<DevBuf> tw;
@@ -427,21 +414,18 @@ int rs_reconstruct_batch_dev_patterns(uint64_t k, uint64_t m, size_t sb, uint64_
     // per-stripe plan: logs u16 | pre RsTab | post RsTab | src i32 | dst i32 (W entries each)
     //                  [| trimmed present rows, matrix path]
     const uint64_t per = W * (2 + 2 * sizeof(RsTab) + 8);
-    void *tmp = nullptr;
-    HIP_TRY(dev_malloc_async(&tmp, n_stripes * per + (use_matrix ? n_stripes * (k + m) : 0) + 256, s));
+    StreamScratch tmp;
+    if ((st = tmp.alloc(n_stripes * per + (use_matrix ? n_stripes * (k + m) : 0) + 256, s))) return st;
     if (use_matrix) {  // evaluate the erasure locator for exactly the k inputs the matrix uses
-      uint8_t *trimmed = static_cast<uint8_t *>(tmp) + n_stripes * per;
-      hipError_t e = launch_trim_present(d_present, present_stride, static_cast<uint32_t>(k), static_cast<uint32_t>(m),
-                                         n_stripes, trimmed, s);
-      if (e != hipSuccess) {
-        (void)hipFreeAsync(tmp, s);
-        return hip_fail(e, "launch_trim_present");
-      }
+      uint8_t *trimmed = tmp.bytes() + n_stripes * per;
+      if ((st = hip_status(launch_trim_present(d_present, present_stride, static_cast<uint32_t>(k),
+                                               static_cast<uint32_t>(m), n_stripes, trimmed, s),
+                           "launch_trim_present")))
+        return st;
       d_present = trimmed;
       present_stride = k + m;
     }
-    uint8_t *base = static_cast<uint8_t *>(tmp);
-    RsTab *pre = reinterpret_cast<RsTab *>(base);
+    RsTab *pre = tmp.at<RsTab>();
     RsTab *post = pre + n_stripes * W;
     int32_t *src = reinterpret_cast<int32_t *>(post + n_stripes * W);
     int32_t *dst = src + n_stripes * W;
@@ -450,57 +434,49 @@ int rs_reconstruct_batch_dev_patterns(uint64_t k, uint64_t m, size_t sb, uint64_
                                        static_cast<uint32_t>(C), static_cast<uint32_t>(W), n_stripes, max_e,
                                        flags & RS_FLAG_QUIRK_D1, low, dexp, dlog, dlw, logs, pre, post, src, dst,
                                        d_status, s);
-    if (e != hipSuccess) {
-      (void)hipFreeAsync(tmp, s);
-      return hip_fail(e, "launch_pattern_plan");
-    }
+    if (e != hipSuccess) return hip_fail(e, "launch_pattern_plan");
     // Per-stripe e x k matrices built on the GPU, then the matrix kernel (40 MACs per
     // column for RS(10,4) instead of the FFT reconstruct's 48 multiplies + masks).
     // Corrected multiply only (under D1 the literal reconstruct uses all received
     // shards); RS_AMD_PATTERNS=fft keeps the FFT kernels.
     if (use_matrix) {
       const uint64_t nk = n_stripes * k;
-      void *mt = nullptr;
       const uint64_t img_bytes = nk * max_e * 16 * sizeof(uint16_t), tab_bytes = nk * max_e * sizeof(RsTab);
-      e = dev_malloc_async(&mt, tab_bytes + img_bytes + nk * 4 + n_stripes * 4 + 256, s);
+      StreamScratch mt;
+      if ((st = mt.alloc(tab_bytes + img_bytes + nk * 4 + n_stripes * 4 + 256, s))) return st;
+      RsTab *mtabs = mt.at<RsTab>();
+      uint16_t *images = mt.at<uint16_t>(tab_bytes);
+      int32_t *srcs = mt.at<int32_t>(tab_bytes + img_bytes);
+      int32_t *nout = srcs + nk;
+      e = launch_pattern_matrix(d_present, present_stride, static_cast<uint32_t>(k), static_cast<uint32_t>(m),
+                                static_cast<uint32_t>(C), static_cast<uint32_t>(W), n_stripes, max_e, logs,
+                                static_cast<const RsTab *>(tw->p),
+                                reinterpret_cast<const RsTab *>(static_cast<const uint8_t *>(tw->p) + off_fft), dexp,
+                                dlog, images, mtabs, srcs, nout, s);
       if (e == hipSuccess) {
-        RsTab *mtabs = static_cast<RsTab *>(mt);
-        uint16_t *images = reinterpret_cast<uint16_t *>(static_cast<uint8_t *>(mt) + tab_bytes);
-        int32_t *srcs = reinterpret_cast<int32_t *>(static_cast<uint8_t *>(mt) + tab_bytes + img_bytes);
-        int32_t *nout = srcs + nk;
-        e = launch_pattern_matrix(d_present, present_stride, static_cast<uint32_t>(k), static_cast<uint32_t>(m),
-                                  static_cast<uint32_t>(C), static_cast<uint32_t>(W), n_stripes, max_e, logs,
-                                  static_cast<const RsTab *>(tw->p),
-                                  reinterpret_cast<const RsTab *>(static_cast<const uint8_t *>(tw->p) + off_fft), dexp,
-                                  dlog, images, mtabs, srcs, nout, s);
-        if (e == hipSuccess) {
-          const KernelChoice km = choose_decode_matrix(max_e, sb, max_nv);
-          DecodeArgs a{};
-          a.orig = static_cast<const uint8_t *>(d_original);
-          a.orig_stripe_stride = orig_stride;
-          a.rec = static_cast<const uint8_t *>(d_recovery);
-          a.rec_stripe_stride = rec_stride;
-          a.out = static_cast<uint8_t *>(d_restored);
-          a.out_stripe_stride = out_stride;
-          a.shard_bytes = sb;
-          a.tab_mat = mtabs;
-          a.pos_src = srcs;
-          a.n_in = static_cast<uint32_t>(k);
-          a.n_out = max_e;
-          a.mat_stride = k * max_e;
-          a.src_stride = k;
-          a.nout = nout;
-          a.tab_pre = a.tab_post = mtabs;  // unused; launch_decode advances them
-          a.pos_dst = srcs;
-          a.contig = contig_ok(sb, km.nv);
-          a.n_stripes = n_stripes;
-          e = launch_decode(km, a, s);
-        }
-        (void)hipFreeAsync(mt, s);
+        const KernelChoice km = choose_decode_matrix(max_e, sb, max_nv);
+        DecodeArgs a{};
+        a.orig = static_cast<const uint8_t *>(d_original);
+        a.orig_stripe_stride = orig_stride;
+        a.rec = static_cast<const uint8_t *>(d_recovery);
+        a.rec_stripe_stride = rec_stride;
+        a.out = static_cast<uint8_t *>(d_restored);
+        a.out_stripe_stride = out_stride;
+        a.shard_bytes = sb;
+        a.tab_mat = mtabs;
+        a.pos_src = srcs;
+        a.n_in = static_cast<uint32_t>(k);
+        a.n_out = max_e;
+        a.mat_stride = k * max_e;
+        a.src_stride = k;
+        a.nout = nout;
+        a.tab_pre = a.tab_post = mtabs;  // unused; launch_decode advances them
+        a.pos_dst = srcs;
+        a.contig = contig_ok(sb, km.nv);
+        a.n_stripes = n_stripes;
+        e = launch_decode(km, a, s);
       }
-      (void)hipFreeAsync(tmp, s);
-      if (e != hipSuccess) return hip_fail(e, "per-stripe matrix reconstruct");
-      return RS_OK;
+      return hip_status(e, "per-stripe matrix reconstruct");
     }
     const KernelChoice kc = low ? choose_decode_w(W, sb, max_nv) : choose_decode(k, m, sb, max_nv);
     DecodeArgs a{};
@@ -524,31 +500,24 @@ int rs_reconstruct_batch_dev_patterns(uint64_t k, uint64_t m, size_t sb, uint64_
     a.contig = kc.variant != Variant::kGeneric && contig_ok(sb, kc.nv);
     if (kc.variant != Variant::kGeneric) {
       a.n_stripes = n_stripes;
-      e = launch_decode(kc, a, s);
-    } else {
-      // launch_decode_generic: the transform plus the FFT's kept rows, per stripe
-      const uint64_t rows = decode_generic_rows(W, a.trunc, a.trunc_fft);
-      const uint64_t cap = slice_stripes(n_stripes, rows * sb);
-      void *scratch = nullptr;
-      e = dev_malloc_async(&scratch, cap * rows * sb, s);
-      for (uint64_t s0 = 0; e == hipSuccess && s0 < n_stripes; s0 += cap) {
-        DecodeArgs b = a;
-        b.orig += s0 * orig_stride;
-        b.rec += s0 * rec_stride;
-        b.out += s0 * out_stride;
-        b.tab_pre += s0 * W;
-        b.tab_post += s0 * W;
-        b.pos_src += s0 * W;
-        b.pos_dst += s0 * W;
-        b.n_stripes = std::min(cap, n_stripes - s0);
-        b.scratch = static_cast<uint8_t *>(scratch);
-        e = launch_decode(kc, b, s);
-      }
-      if (scratch) (void)hipFreeAsync(scratch, s);
+      return hip_status(launch_decode(kc, a, s), "launch_decode (patterns)");
     }
-    (void)hipFreeAsync(tmp, s);
-    if (e != hipSuccess) return hip_fail(e, "launch_decode (patterns)");
-    return RS_OK;
+    // launch_decode_generic: the transform plus the FFT's kept rows, per stripe
+    const uint64_t rows = decode_generic_rows(W, a.trunc, a.trunc_fft);
+    const uint64_t cap = slice_stripes(n_stripes, rows * sb);
+    return in_scratch_slices(n_stripes, cap, cap * rows * sb, s, [&](uint64_t s0, uint64_t cnt, uint8_t *scratch) {
+      DecodeArgs b = a;
+      b.orig += s0 * orig_stride;
+      b.rec += s0 * rec_stride;
+      b.out += s0 * out_stride;
+      b.tab_pre += s0 * W;
+      b.tab_post += s0 * W;
+      b.pos_src += s0 * W;
+      b.pos_dst += s0 * W;
+      b.n_stripes = cnt;
+      b.scratch = scratch;
+      return hip_status(launch_decode(kc, b, s), "launch_decode (patterns)");
+    });
   });
 }
 

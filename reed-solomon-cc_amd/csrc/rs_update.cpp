@@ -27,6 +27,17 @@ bool coef_logs(uint64_t k, uint64_t m, std::vector<uint16_t> &cl) {
   return true;
 }
 
+void encode_columns(int hr, uint64_t k, uint64_t m, uint64_t P, const std::vector<uint16_t> &d,
+                    std::vector<uint16_t> &p) {
+  std::vector<uint16_t> col(k), out(m);
+  for (uint64_t q = 0; q < P; q++) {
+    for (uint64_t j = 0; j < k; j++) col[j] = d[j * P + q];
+    if (hr == 0) scalar_encode_low(col.data(), k, m, false, out.data());
+    else scalar_encode(col.data(), k, m, false, false, out.data());
+    for (uint64_t r = 0; r < m; r++) p[r * P + q] = out[r];
+  }
+}
+
 namespace {
 
 static_assert(RS_UPDATE_NONE == kUpdateNone && RS_ERR_INVALID_SHARD_INDEX == kUpdateInvalidIndex &&
@@ -34,26 +45,11 @@ static_assert(RS_UPDATE_NONE == kUpdateNone && RS_ERR_INVALID_SHARD_INDEX == kUp
               "the kernels' values are the ABI's");
 
 // Per (device, k, m): cl [k][m], the logs of the encode's coefficients
-struct UpdatePlan {
-  std::shared_ptr<DevBuf> buf;
-  const uint16_t *cl() const { return static_cast<const uint16_t *>(buf->p); }
-};
-PlanCache<UpdatePlan> g_update_plans;
-
-int get_update_plan(int dev, uint64_t k, uint64_t m, std::shared_ptr<UpdatePlan> &out) {
-  const std::string key = std::to_string(dev) + "/" + std::to_string(k) + "/" + std::to_string(m);
-  {
-    std::lock_guard<std::mutex> lk(g_plan_mu);
-    if ((out = g_update_plans.find(key))) return RS_OK;
-  }
-  alloc_point();
-  auto p = std::make_shared<UpdatePlan>();
-  std::vector<uint16_t> cl;
-  if (!coef_logs(k, m, cl)) return fail(RS_ERR_DEVICE, "update: the code has a zero coefficient");
-  if (int st = upload(cl.data(), cl.size() * sizeof(uint16_t), dev, p->buf)) return st;
-  std::lock_guard<std::mutex> lk(g_plan_mu);
-  out = g_update_plans.insert(key, p);
-  return RS_OK;
+int get_update_plan(int dev, uint64_t k, uint64_t m, std::shared_ptr<CodePlan> &out) {
+  return get_code_plan(g_update_plans, dev, k, m, [&](std::vector<uint16_t> &cl) -> int {
+    if (!coef_logs(k, m, cl)) return fail(RS_ERR_DEVICE, "update: the code has a zero coefficient");
+    return RS_OK;
+  }, out);
 }
 
 // The scratch of one slice, per stripe: the tables of max_u slots, the slot list and the live
@@ -71,32 +67,26 @@ struct Scratch {
 int update_slices(int dev, uint64_t k, uint64_t m, uint64_t sb, uint64_t n, uint32_t max_u, const uint32_t *index,
                   uint64_t istride, const uint8_t *d_old, const uint8_t *d_new, uint64_t cstride, uint8_t *rec,
                   uint64_t rstride, int32_t *status, hipStream_t s) {
-  std::shared_ptr<UpdatePlan> plan;
+  std::shared_ptr<CodePlan> plan;
   const uint16_t *dexp = nullptr, *dlog = nullptr, *dlw = nullptr;
   int st;
   if ((st = get_update_plan(dev, k, m, plan))) return st;
   if ((st = device_tables(dev, &dexp, &dlog, &dlw))) return st;
   const Scratch L(n, m, max_u);
-  void *mem = nullptr;
-  HIP_TRY(dev_malloc_async(&mem, L.bytes, s));
-  uint8_t *base = static_cast<uint8_t *>(mem);
-  RsTab *tabs = reinterpret_cast<RsTab *>(base);
-  uint32_t *list = reinterpret_cast<uint32_t *>(base + L.list), *live = reinterpret_cast<uint32_t *>(base + L.live);
   const uint32_t k32 = static_cast<uint32_t>(k), m32 = static_cast<uint32_t>(m);
-  for (uint64_t s0 = 0; st == RS_OK && s0 < n; s0 += L.per) {
-    const uint64_t cnt = std::min(L.per, n - s0);
+  return in_scratch_slices(n, L.per, L.bytes, s, [&](uint64_t s0, uint64_t cnt, uint8_t *base) {
+    RsTab *tabs = reinterpret_cast<RsTab *>(base);
+    uint32_t *list = reinterpret_cast<uint32_t *>(base + L.list), *live = reinterpret_cast<uint32_t *>(base + L.live);
     const char *what = "launch_update_prepare";
-    hipError_t e = launch_update_prepare(index + s0 * istride, istride, max_u, cnt, k32, m32, plan->cl(), dexp, dlog,
+    hipError_t e = launch_update_prepare(index + s0 * istride, istride, max_u, cnt, k32, m32, plan->u16(), dexp, dlog,
                                          tabs, list, live, status ? status + s0 : nullptr, s);
     if (e == hipSuccess) {
       what = "launch_update_apply";
       e = launch_update_apply(d_old ? d_old + s0 * cstride : nullptr, d_new + s0 * cstride, cstride,
                               rec + s0 * rstride, rstride, sb, cnt, m32, max_u, list, live, tabs, s);
     }
-    if (e != hipSuccess) st = hip_fail(e, what);
-  }
-  (void)hipFreeAsync(mem, s);
-  return st;
+    return hip_status(e, what);
+  });
 }
 
 bool overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes) {
@@ -105,11 +95,6 @@ bool overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes) {
 }
 
 }  // namespace
-
-void release_update() {
-  std::lock_guard<std::mutex> lk(g_plan_mu);
-  g_update_plans.clear();
-}
 
 }  // namespace host
 }  // namespace rs
@@ -159,31 +144,17 @@ int rs_update_selftest(uint64_t k, uint64_t m, uint32_t max_u, int trials, uint6
     if (k == 0) return fail(RS_ERR_INVALID_ARGUMENT, "original_count == 0");
     const int hr = use_high_rate(k, m);
     if (hr < 0) return fail(-hr, "unsupported shard count (root.zig:397-415)");
-    uint64_t state = seed * 0x9E3779B97F4A7C15ull + 1;
-    auto rnd = [&]() {  // splitmix64
-      uint64_t z = (state += 0x9E3779B97F4A7C15ull);
-      z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-      z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-      return z ^ (z >> 31);
-    };
+    SplitMix64 rnd(seed);
     uint64_t bad = 0;
     std::vector<uint16_t> cl;
     if (!coef_logs(k, m, cl)) bad++;  // a zero coefficient
     constexpr uint64_t P = 4;         // symbols per shard
-    std::vector<uint16_t> data(k * P), stored(m * P), want(m * P), col(k), out(m);
-    auto encode = [&](const std::vector<uint16_t> &d, std::vector<uint16_t> &p) {
-      for (uint64_t q = 0; q < P; q++) {
-        for (uint64_t j = 0; j < k; j++) col[j] = d[j * P + q];
-        if (hr == 0) scalar_encode_low(col.data(), k, m, false, out.data());
-        else scalar_encode(col.data(), k, m, false, false, out.data());
-        for (uint64_t r = 0; r < m; r++) p[r * P + q] = out[r];
-      }
-    };
+    std::vector<uint16_t> data(k * P), stored(m * P), want(m * P);
     const uint64_t u_max = std::min<uint64_t>(max_u, k);
     std::vector<uint64_t> pick(k);
     for (int t = 0; bad == 0 && u_max > 0 && t < trials; t++) {
       for (auto &x : data) x = static_cast<uint16_t>(rnd());
-      encode(data, stored);
+      encode_columns(hr, k, m, P, data, stored);
       // 1..u_max distinct originals: the head of a partial Fisher-Yates shuffle
       const uint64_t u = 1 + rnd() % u_max;
       for (uint64_t j = 0; j < k; j++) pick[j] = j;
@@ -196,7 +167,7 @@ int rs_update_selftest(uint64_t k, uint64_t m, uint32_t max_u, int trials, uint6
           for (uint64_t r = 0; r < m; r++) stored[r * P + q] ^= mul16(delta, cl[j * m + r]);
         }
       }
-      encode(data, want);
+      encode_columns(hr, k, m, P, data, want);
       for (uint64_t i = 0; i < m * P; i++) bad += stored[i] != want[i];
     }
     if (mismatches) *mismatches = bad;

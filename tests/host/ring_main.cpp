@@ -1,10 +1,11 @@
 // ring_main.cpp — host-only checks of the knob table (rs_env.hpp) and of the HIP-free parts of
-// the host-batch ring (rs_host_ring.hpp). Built and run by tests/test_host_ring.py; exits 0
+// the host-batch ring (rs_host_ring.hpp) and of the scratch slicing (rs_slices.hpp). Built and run by tests/test_host_ring.py; exits 0
 // when every check holds and prints each failed one otherwise.
 #include <cstdio>
 
 #include "rs_env.hpp"
 #include "rs_host_ring.hpp"
+#include "rs_slices.hpp"
 
 using namespace rs;
 using Runs = std::vector<std::pair<uint64_t, uint64_t>>;
@@ -189,11 +190,51 @@ static void check_slice_stripes() {
   }
 }
 
+// The two rules of rs_slices.hpp, worked out here. Greedy (fit_stripes): floor(cap / stripe) stripes
+// per slice, at least 1, at most n. Balanced (slice_stripes): the fewest slices the greedy rule
+// allows under RS_AMD_SCRATCH_CAP_MB, then the stripes spread evenly over them.
+static void check_scratch_slices() {
+  const uint64_t GiB = 1ull << 30, MiB = 1ull << 20;
+  CHECK(host::fit_stripes(100, 1000, 1001) == 1);       // one stripe exceeds the cap
+  CHECK(host::fit_stripes(100, 1000, 1000) == 1);
+  CHECK(host::fit_stripes(7, GiB, 1000) == 7);          // everything fits
+  CHECK(host::fit_stripes(100, 1000, 10) == 100);       // exactly
+  CHECK(host::fit_stripes(101, 1000, 10) == 100);
+  // RS(10,4) and RS(10,4) + 2 restored rows, shards padded to 65600 bytes, 1200 stripes in 1 GiB:
+  // 1073741824 / 918400 = 1169.1..., 1073741824 / 1049600 = 1023.0009...
+  CHECK(14 * 65600 == 918400 && 1169ull * 918400 <= GiB && 1170ull * 918400 > GiB);
+  CHECK(16 * 65600 == 1049600 && 1023ull * 1049600 <= GiB && 1024ull * 1049600 > GiB);
+  CHECK(host::fit_stripes(1200, GiB, 14 * 65600) == 1169);
+  CHECK(host::fit_stripes(1200, GiB, 16 * 65600) == 1023);
+
+  set(env::SCRATCH_CAP_MB, "1");
+  CHECK(host::scratch_cap() == MiB);
+  CHECK(host::slice_stripes(9, 256 << 10) == 3);   // 4 fit: 3 slices of 3, not 4 + 4 + 1
+  CHECK(host::slice_stripes(8, 256 << 10) == 4);   // 2 slices of 4
+  CHECK(host::slice_stripes(5, 256 << 10) == 3);   // 2 slices: 3 + 2
+  CHECK(host::slice_stripes(4, 256 << 10) == 4);   // one slice
+  CHECK(host::slice_stripes(5, 2 * MiB) == 1);     // one stripe exceeds the cap: one per slice
+  for (uint64_t stripe : std::vector<uint64_t>{1, 1000, 65600, 300000, MiB, MiB + 1})
+    for (uint64_t n : std::vector<uint64_t>{1, 2, 3, 9, 16, 17, 1000, 65541}) {
+      const uint64_t per = host::slice_stripes(n, stripe);
+      const uint64_t fit = std::max<uint64_t>(1, MiB / stripe);  // stripes the cap holds
+      const uint64_t fewest = (n + std::min(fit, n) - 1) / std::min(fit, n), slices = (n + per - 1) / per;
+      CHECK(per >= 1 && per <= n);
+      if (stripe <= MiB) CHECK(per * stripe <= MiB);
+      CHECK(slices * per >= n);
+      CHECK(slices == fewest);              // no more slices than the cap forces
+      CHECK(slices * per - n < slices);     // even: no slice is short by a whole round
+    }
+  set(env::SCRATCH_CAP_MB, nullptr);
+  CHECK(host::scratch_cap() == host::kScratchCap);
+}
+
 int main() {
   check_env();
   check_host_copy();
   check_present_runs();
   check_slice_stripes();
+  check_scratch_slices();
   if (g_failed) return 1;
   std::printf("ring_main: ok\n");
   return 0;

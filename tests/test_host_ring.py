@@ -1,5 +1,6 @@
-"""Host-only checks of the knob table's readers and of the HIP-free parts of the host-batch ring
-(csrc/rs_env.hpp, csrc/rs_host_ring.hpp): tests/host/ring_main.cpp, built as a plain C++ program."""
+"""Host-only checks of the knob table's readers, of the HIP-free parts of the host-batch ring and of
+the scratch slicing rules (csrc/rs_env.hpp, csrc/rs_host_ring.hpp, csrc/rs_slices.hpp):
+tests/host/ring_main.cpp, built as a plain C++ program."""
 import os
 import shutil
 import subprocess
