@@ -198,7 +198,8 @@ const char *rs_verify_kernel_name(uint64_t original_count, uint64_t recovery_cou
  * RS_LOCATE_RECOVERY_SET: 0 at each disagreeing recovery shard; RS_LOCATE_CLEAN and
  * RS_LOCATE_UNLOCATED: all 1. A row can be passed as it is to rs_reconstruct_batch_dev_patterns
  * with max_e = 1: a corrupt original is restored from the other shards; a stripe whose bad
- * shards are recovery shards has e_s = 0 and is healed by encoding it again.
+ * shards are recovery shards has e_s = 0 there and is healed by rs_rebuild_batch_dev (below), which
+ * takes the same rows and puts back originals and recovery shards alike.
  * d_counts (device, optional): 4 words, the stripes that are clean, located to a single shard,
  * a recovery set, unlocated. Neither input buffer is written.
  * Guarantee: with at most one corrupt shard in a stripe and m >= 2 the answer is exact. With two
@@ -282,6 +283,62 @@ int rs_update_batch_dev(uint64_t original_count, uint64_t recovery_count, size_t
  * coefficient). RS_ERR_INVALID_ARGUMENT for original_count == 0. */
 int rs_update_selftest(uint64_t original_count, uint64_t recovery_count, uint32_t max_u, int trials, uint64_t seed,
                        uint64_t *mismatches);
+
+/* Rebuild (heal): every lost shard of a stripe comes back, recovery shards included, each stripe
+ * with its own set of lost shards. What a node or disk failure under rotated parity needs: the
+ * failed node held a data shard of some stripes and a parity shard of others.
+ * d_present (device): the rows of rs_reconstruct_batch_dev_patterns (k + m flags per stripe, row
+ * stride present_stride, 0 = k + m), so rs_locate_batch_dev's d_present rows can be passed as they
+ * are. For stripe s let E be its missing originals, ascending (e_o of them), Q its missing recovery
+ * shards, ascending (e_r), e_s = e_o + e_r.
+ * d_rebuilt (device): [n_stripes][max_e][shard_bytes] (stripe stride rebuilt_stripe_stride, 0 =
+ * packed). Slots [0, e_o) of the stripe's row receive the originals E, slots [e_o, e_s) the
+ * recovery shards Q, byte for byte what rs_encode_batch_dev writes for the stripe's true
+ * originals. Slots >= e_s are not written, nothing past max_e slots is written, no input is
+ * written, and the contents of missing slots never influence a result.
+ * d_status (device, n_stripes int32, may be NULL; every entry written): RS_OK (a stripe with
+ * nothing missing too: nothing of it is written); RS_ERR_NOT_ENOUGH_SHARDS with fewer than k shards
+ * present (e_s > m): nothing of the stripe is written; RS_ERR_INVALID_ARGUMENT with e_s > max_e: the
+ * first max_e slots in the order above are written, as rs_reconstruct_batch_dev_patterns does.
+ * Validated on the host before any device call, in this order: original_count == 0
+ * (RS_ERR_TOO_FEW_ORIGINAL_SHARDS); the encode's checks of the counts and shard_bytes; n_stripes
+ * == 0 or max_e == 0: RS_OK, nothing written; then RS_ERR_INVALID_ARGUMENT for a NULL d_present,
+ * d_original, d_recovery or d_rebuilt, max_e > m, a stride below its row size, flags != 0 (as for
+ * rs_locate_batch_dev and rs_update_batch_dev: under RS_FLAG_QUIRK_D1 and RS_FLAG_QUIRK_D2 a lost
+ * recovery shard is no linear function of the syndromes), with shard_bytes % 64 == 0 a data pointer
+ * or stripe stride that is no multiple of 4, and a d_rebuilt range that overlaps either input range.
+ * Accepts everything rs_reconstruct_batch_dev_patterns accepts with flags == 0: tails, any even
+ * shard_bytes, 4- and 8-byte-aligned layouts, wide and low-rate codes, strides.
+ * Two forms. Fast: codes with k <= 256, m <= 8 on whole 4 KiB units with
+ * 16-byte-aligned buffers and strides run one pass of the code's syndrome network
+ * (rs_psyn_rebuild_k<k>_m<m>_<hash>, hipRTC) after k_psyn_rebuild_plan: k + e_s shard rows of
+ * traffic per stripe. While that kernel compiles in the background (larger codes; RS_AMD_JIT_SYNC=1
+ * compiles in the caller) a call takes the general form; rs_last_kernels reports what ran.
+ * General, everything else, in slices of stripes (scratch at most RS_AMD_SCRATCH_CAP_MB, at least
+ * one stripe): the per-stripe reconstruct into slots [0, e_o), k_rebuild_gather of the stripe's
+ * originals into a scratch, the encode of that scratch, k_rebuild_pick of rows Q: about
+ * 3k + m + e_o + 2 e_r rows per stripe. It is the correct-everywhere path, not the fast one.
+ * Out of scope: rebuilding in place into the missing slots, a *_host form, a batch-wide-pattern
+ * form with compiled-in patterns, a fused wide-code form. */
+int rs_rebuild_batch_dev(uint64_t original_count, uint64_t recovery_count, size_t shard_bytes, uint64_t n_stripes,
+                         const uint8_t *d_present, uint64_t present_stride, uint32_t max_e,
+                         const void *d_original, uint64_t original_stripe_stride,
+                         const void *d_recovery, uint64_t recovery_stripe_stride,
+                         void *d_rebuilt, uint64_t rebuilt_stripe_stride, int32_t *d_status,
+                         uint32_t flags, rs_stream_t stream);
+/* The path a rebuild is planned to take: "psyn_rebuild_k<k>_m<m>" (the fast form, given aligned
+ * buffers), else "<rs_patterns_kernel_name>+rebuild_gather+<rs_encode_kernel_name>+rebuild_pick". */
+const char *rs_rebuild_kernel_name(uint64_t k, uint64_t m, size_t shard_bytes, uint32_t max_e);
+/* Generate the rebuild variant of the code's syndrome network and compile it for gfx950 with
+ * hipRTC (no device). RS_ERR_INVALID_ARGUMENT where the code has no such kernel (k > 256, m > 8,
+ * low rate). */
+int rs_rebuild_compile_check(uint64_t k, uint64_t m, double *compile_ms, uint64_t *code_bytes);
+/* Host check of the rebuild algebra (no device): k_psyn_rebuild_plan's coefficients on scalar
+ * symbols, over `trials` random stripes of a few symbols per shard with random sets of lost shards
+ * (among them recovery shards only, originals only and e_s = m), the missing slots poisoned; the
+ * rebuilt symbols must equal the data and the scalar encode. *mismatches = wrong symbols (or 1 for
+ * a zero coefficient or a singular block). RS_ERR_INVALID_ARGUMENT for original_count == 0. */
+int rs_rebuild_selftest(uint64_t k, uint64_t m, int trials, uint64_t seed, uint64_t *mismatches);
 
 /* -------------------------------------- host-resident batches (end to end)
  * Same layouts and semantics as the *_dev calls, but the batch lives in HOST

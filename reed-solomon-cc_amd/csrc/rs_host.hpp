@@ -1,12 +1,13 @@
 // rs_host.hpp — internal interface of the host codec (librs_amd.so): validation and
 // error reporting, plan caches, kernel selection, plans, and the entry points the
 // C ABI files (rs_batch_dev.cpp, rs_patterns.cpp, rs_lowrate.cpp, rs_host_batch.cpp,
-// rs_oneshot.cpp, rs_verify.cpp, rs_locate.cpp, rs_update.cpp) share: the stream-ordered scratch
+// rs_oneshot.cpp, rs_verify.cpp, rs_locate.cpp, rs_update.cpp, rs_rebuild.cpp) share: the stream-ordered scratch
 // (StreamScratch, the only place that frees one) and the slice loop over it (in_scratch_slices,
 // sized by rs_slices.hpp), the shard-tail helpers, and the shell of the scrub family (argument
 // front, encode-and-compare step, CodePlan). Host-side mirror of root.zig's checks and error
 // precedence; every device computation runs in the precompiled kernels
-// (rs_kernels.hip, rs_phase_kernels.hip, rs_plan_kernels.hip, rs_locate_kernels.hip, rs_update_kernels.hip) or in a hipRTC kernel (rs_jit / rs_fftnet / rs_psyn); there is no CPU compute path.
+// (rs_kernels.hip, rs_phase_kernels.hip, rs_plan_kernels.hip, rs_locate_kernels.hip, rs_update_kernels.hip,
+// rs_rebuild_kernels.hip) or in a hipRTC kernel (rs_jit / rs_fftnet / rs_psyn); there is no CPU compute path.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -417,6 +418,14 @@ uint32_t pdec_after();
 size_t pdec_queue();
 // admit the pattern `key` of code (dev, k, m) to the budget (true if already admitted)
 bool pdec_admit(int dev, uint64_t k, uint64_t m, const std::string &key);
+// the per-stripe syndrome network serves this shape (RS_AMD_PATTERNS, RS_AMD_JIT, psyn::supports)
+bool psyn_enabled(uint64_t k, uint64_t m, uint64_t sb, uint32_t flags);
+// The fast form of rs_rebuild_batch_dev (rs_rebuild.cpp): k_psyn_rebuild_plan, then the rebuild
+// variant of the code's syndrome network. *ran = false with RS_OK while that kernel compiles in
+// the background or where it is unavailable: nothing was launched, the caller takes the general form.
+int psyn_rebuild(int dev, uint64_t k, uint64_t m, uint64_t sb, uint64_t n, const uint8_t *d_present,
+                 uint64_t present_stride, uint32_t max_e, const uint8_t *orig, uint64_t ostride, const uint8_t *rec,
+                 uint64_t rstride, uint8_t *out, uint64_t outstride, int32_t *d_status, hipStream_t s, bool *ran);
 // cl[j * m + r] = log c[r][j] in [0, 65535), the encode's coefficients (parity[r] = sum_j c[r][j]
 // * original[j] under the corrected arithmetic), from the scalar encode of unit vectors (the
 // low-rate encode for low-rate codes). false if a coefficient is zero (never in an MDS code).

@@ -1,6 +1,6 @@
 // rs_internal.hpp — launch interface between the host codec (rs_host.hpp and the files behind it) and
 // the HIP kernels (rs_kernels.hip, rs_phase_kernels.hip, rs_plan_kernels.hip, rs_locate_kernels.hip,
-// rs_update_kernels.hip). Not part of the public ABI.
+// rs_update_kernels.hip, rs_rebuild_kernels.hip). Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -199,6 +199,14 @@ hipError_t launch_psyn_plan(const uint8_t *present, uint64_t present_stride, uin
                             uint32_t max_e, uint64_t n, const uint16_t *G, const uint16_t *d_exp, const uint16_t *d_log,
                             uint32_t *plan, uint32_t plan_dw, int32_t *status, hipStream_t s);
 
+// The same for the rebuild variant of that kernel (psyn::Spec::rebuild, rs_rebuild.cpp): lost
+// recovery shards are outputs too. plan [n][plan_dw], plan_dw >= psyn::rebuild_plan_dwords(k, m);
+// status per the contract of rs_rebuild_batch_dev (counts every missing shard against max_e)
+hipError_t launch_psyn_rebuild_plan(const uint8_t *present, uint64_t present_stride, uint32_t k, uint32_t m,
+                                    uint32_t max_e, uint64_t n, const uint16_t *G, const uint16_t *d_exp,
+                                    const uint16_t *d_log, uint32_t *plan, uint32_t plan_dw, int32_t *status,
+                                    hipStream_t s);
+
 // Per-stripe plan of the wide-code path: FFT mask block (dmw words) + solve header
 // (rs_plan_kernels.hip k_wps_plan / k_wps_plan_wave); plan_dw >= dmw + 2 + 64 + 64 * cs,
 // cs = wps_coef_stride(max_e) (coefficients per syndrome: 8, or max_e rounded up to 8), m <= 64
@@ -277,6 +285,24 @@ hipError_t launch_update_prepare(const uint32_t *index, uint64_t index_stride, u
 hipError_t launch_update_apply(const uint8_t *d_old, const uint8_t *d_new, uint64_t change_stride, uint8_t *rec,
                                uint64_t rec_stride, uint64_t sb, uint64_t n, uint32_t m, uint32_t max_u,
                                const uint32_t *list, const uint32_t *live, const RsTab *tabs, hipStream_t s);
+
+// Rebuild, general form (rs_rebuild.cpp, rs_rebuild_kernels.hip): meta [n][rebuild_meta_words(k, m)]
+// per stripe: [0] the recovery slots to write, min(e_s, max_e) - e_o (0: the stripe is skipped:
+// undecodable, no recovery shard missing, or no slot left for one), [1] e_o, [2 + j] for j < k the
+// restored slot of original j or kRebuildPresent, [2 + k + i] the i-th missing recovery row.
+constexpr uint32_t kRebuildPresent = 0xFFFFFFFFu;
+constexpr uint64_t rebuild_meta_words(uint64_t k, uint64_t m) { return (2 + k + m + 3) / 4 * 4; }  // 16-byte blocks
+// meta and the final status (may be NULL): RS_OK, 2 with fewer than k present, 14 with e_s > max_e
+hipError_t launch_rebuild_prepare(const uint8_t *present, uint64_t present_stride, uint32_t k, uint32_t m,
+                                  uint32_t max_e, uint64_t n, uint32_t *meta, int32_t *status, hipStream_t s);
+// data [n][k][sb] (packed) <- original j where present, else its restored slot of `rebuilt`
+hipError_t launch_rebuild_gather(const uint8_t *orig, uint64_t orig_stride, const uint8_t *rebuilt,
+                                 uint64_t rebuilt_stride, uint64_t sb, uint64_t n, uint32_t k, uint32_t m,
+                                 const uint32_t *meta, uint8_t *data, hipStream_t s);
+// rebuilt slots [e_o, e_o + meta[0]) <- rows Q of par [n][m][sb] (packed). Both copy kernels use
+// 16-byte, dword or byte accesses by what the buffers, strides and sb allow (_x16 / _x4 / _x1)
+hipError_t launch_rebuild_pick(const uint8_t *par, uint64_t sb, uint64_t n, uint32_t k, uint32_t m, uint32_t max_e,
+                               const uint32_t *meta, uint8_t *rebuilt, uint64_t rebuilt_stride, hipStream_t s);
 
 // Engine shims (generic, in place on a single-stripe work buffer)
 hipError_t launch_engine_fft(uint8_t *work, uint64_t shard_bytes, uint64_t pos, uint64_t size, uint64_t trunc,

@@ -136,6 +136,8 @@ struct PsynPlan {
   bool failed = false;
   psyn::Spec spec;
   std::shared_ptr<DevBuf> G;
+  bool rebuild_failed = false;
+  psyn::Spec rebuild_spec;  // spec with rebuild set (rs_rebuild_batch_dev), filled on first use
 };
 std::map<std::string, std::shared_ptr<PsynPlan>> g_psyn_plans;
 
@@ -218,12 +220,55 @@ bool fdec_patterns_enabled(uint64_t k, uint64_t m, uint64_t sb, uint32_t flags, 
   return fdec_mode() == 1 || 5ull * max_e >= 3ull * m || sb % jit::kUnitBytes != 0;
 }
 
-bool psyn_enabled(uint64_t k, uint64_t m, uint64_t sb, uint32_t flags) {
+// the rebuild variant of the code's kernel (psyn::Spec::rebuild), compiled on first use
+const jit::Kernel *psyn_rebuild_kernel(PsynPlan &p) {
+  std::lock_guard<std::mutex> lk(p.mu);
+  if (p.rebuild_failed) return nullptr;
+  if (p.rebuild_spec.k == 0) {
+    p.rebuild_spec = p.spec;
+    p.rebuild_spec.rebuild = true;
+  }
+  std::string err;
+  bool pending = false;
+  const jit::Kernel *k = psyn::get(p.rebuild_spec, err, pending);
+  if (!k && !pending) {
+    p.rebuild_failed = true;
+    warn_once_per_reason("[rs_amd] rebuild syndrome network unavailable, using the general form: ", err);
+  }
+  return k;
+}
+
+}  // namespace
+
+bool rs::host::psyn_enabled(uint64_t k, uint64_t m, uint64_t sb, uint32_t flags) {
   return !(flags & RS_FLAG_QUIRK_D1) && !d2_drops_chunk(k, m, flags) &&
          patterns_auto() && jit::enabled() && psyn::supports(k, m, sb);
 }
 
-}  // namespace
+int rs::host::psyn_rebuild(int dev, uint64_t k, uint64_t m, uint64_t sb, uint64_t n, const uint8_t *d_present,
+                           uint64_t present_stride, uint32_t max_e, const uint8_t *orig, uint64_t ostride,
+                           const uint8_t *rec, uint64_t rstride, uint8_t *out, uint64_t outstride, int32_t *d_status,
+                           hipStream_t s, bool *ran) {
+  *ran = false;
+  std::shared_ptr<PsynPlan> pp;
+  int st = psyn_plan(dev, k, m, 0, pp);
+  if (st) return st;
+  const jit::Kernel *pk = psyn_rebuild_kernel(*pp);
+  if (!pk) return RS_OK;  // compiling in the background, or unavailable: the general form
+  const uint16_t *dexp, *dlog, *dlw;
+  if ((st = device_tables(dev, &dexp, &dlog, &dlw))) return st;
+  const uint32_t k32 = static_cast<uint32_t>(k), m32 = static_cast<uint32_t>(m);
+  const uint32_t pdw = psyn::rebuild_plan_dwords(k32, m32);
+  StreamScratch blk;
+  if ((st = blk.alloc(n * pdw * sizeof(uint32_t), s))) return st;
+  *ran = true;
+  hipError_t e = launch_psyn_rebuild_plan(d_present, present_stride, k32, m32, max_e, n,
+                                          static_cast<const uint16_t *>(pp->G->p), dexp, dlog, blk.at<uint32_t>(), pdw,
+                                          d_status, s);
+  if (e == hipSuccess)
+    e = psyn::launch(*pk, pp->rebuild_spec, orig, ostride, rec, rstride, out, outstride, sb, n, blk.at<uint32_t>(), s);
+  return hip_status(e, "rebuild syndrome network");
+}
 
 void rs::host::release_patterns() {
   std::lock_guard<std::mutex> lk(g_plan_mu);

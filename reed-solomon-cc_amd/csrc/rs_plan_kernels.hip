@@ -2,7 +2,7 @@
 // own erasure pattern per stripe needs before the codec kernels run, computed on the device
 // from the present rows. Scalar GF(2^16) code (log / exp tables, one symbol per thread): the
 // erasure locator (k_erasure_logs), the multiplier tables and maps of each path
-// (k_pattern_tables, k_pattern_images / k_pattern_mtabs, k_psyn_plan, k_wps_plan,
+// (k_pattern_tables, k_pattern_images / k_pattern_mtabs, k_psyn_plan, k_psyn_rebuild_plan, k_wps_plan,
 // k_wps_plan_wave, k_fdec_block) and the present rows trimmed to k shards (k_trim_present).
 #include <hip/hip_runtime.h>
 
@@ -373,6 +373,91 @@ __global__ __launch_bounds__(64) void k_psyn_plan(const uint8_t *__restrict__ pr
   pl[nw + 1] = e < max_e ? e : max_e;
 }
 
+// The plan of the rebuild variant (psyn::Spec::rebuild): the lost recovery
+// shards Q are outputs as well. Absent recovery rows are read as zero, so for q in Q the network
+// leaves s_q = Enc_q(data, erased read as 0), and p_q = s_q ^ sum_t G[q][E_t] x_t
+// = s_q ^ sum_{r in R} (G[q][E] A^-1)[i(r)] s_r. Block per stripe (u32): [0, nw) erased mask,
+// [nw] R (the rows whose p_r is loaded), [nw + 1] outputs stored = min(e_s, max_e), [nw + 2] the
+// rows used in the solve, R | Q, then [nw + 3 + r * m + j] the coefficient of s_r in output j:
+// j < e_o row j of A^-1 as above; j = e_o + q the products at R, the field's one at row Q_q.
+__global__ __launch_bounds__(64) void k_psyn_rebuild_plan(const uint8_t *__restrict__ present, uint64_t present_stride,
+                                                          uint32_t k, uint32_t m, uint32_t max_e, uint64_t n,
+                                                          const uint16_t *__restrict__ G,
+                                                          const uint16_t *__restrict__ exp,
+                                                          const uint16_t *__restrict__ log, uint32_t *__restrict__ plan,
+                                                          uint32_t plan_dw, int32_t *__restrict__ status) {
+  const uint64_t s = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (s >= n) return;
+  const uint8_t *pr = present + s * present_stride;
+  uint32_t *pl = plan + s * plan_dw;
+  const uint32_t nw = (k + 31) / 32;
+  uint32_t e = 0, er = 0;
+  for (uint32_t i = 0; i < k; i++) e += pr[i] ? 0 : 1;
+  for (uint32_t r = 0; r < m; r++) er += pr[k + r] ? 0 : 1;
+  const uint32_t es = e + er;
+  if (status) status[s] = es > m ? 2 : (es > max_e ? 14 : 0);
+  for (uint32_t w = 0; w < nw + 3; w++) pl[w] = 0;
+  if (es > m || es == 0) return;  // fewer than k present, or nothing missing (e <= present recovery from here)
+  uint32_t E[kPsynMaxM], R[kPsynMaxM], Q[kPsynMaxM], rm = 0, qm = 0;
+  for (uint32_t i = 0, c = 0; i < k && c < e; i++)
+    if (!pr[i]) E[c++] = i;
+  for (uint32_t r = 0, c = 0, q = 0; r < m; r++) {
+    if (pr[k + r]) {
+      if (c < e) R[c++] = r, rm |= 1u << r;
+    } else {
+      Q[q++] = r, qm |= 1u << r;
+    }
+  }
+  // Gauss-Jordan on [A | I] over GF(2^16) (no step when no original is missing)
+  uint32_t A[kPsynMaxM][2 * kPsynMaxM];
+  for (uint32_t i = 0; i < e; i++)
+    for (uint32_t j = 0; j < 2 * e; j++) A[i][j] = j < e ? G[R[i] * k + E[j]] : (j - e == i ? 1u : 0u);
+  for (uint32_t c = 0; c < e; c++) {
+    uint32_t piv = c;
+    while (piv < e && A[piv][c] == 0) piv++;
+    if (piv == e) {  // singular: not an MDS code (the host keeps such codes off this path)
+      if (status) status[s] = 15;  // RS_ERR_DEVICE: nothing rebuilt
+      return;
+    }
+    for (uint32_t j = 0; j < 2 * e; j++) {
+      const uint32_t t = A[c][j];
+      A[c][j] = A[piv][j];
+      A[piv][j] = t;
+    }
+    const uint32_t inv = exp[(65535u - log[A[c][c]]) % 65535u];
+    for (uint32_t j = 0; j < 2 * e; j++) A[c][j] = gf_mul_d(A[c][j], inv, exp, log);
+    for (uint32_t i = 0; i < e; i++)
+      if (i != c && A[i][c]) {
+        const uint32_t f = A[i][c];
+        for (uint32_t j = 0; j < 2 * e; j++) A[i][j] ^= gf_mul_d(f, A[c][j], exp, log);
+      }
+  }
+  const uint16_t *cantor = G + m * k;
+  for (uint32_t r = 0; r < m; r++) {
+    int32_t ir = -1;
+    for (uint32_t i = 0; i < e; i++) ir = R[i] == r ? static_cast<int32_t>(i) : ir;
+    for (uint32_t j = 0; j < m; j++) {
+      uint32_t c = 0;
+      if (j < e) {
+        c = ir >= 0 ? A[j][e + ir] : 0u;  // x_j += A^-1[j][i] s_{R_i}
+      } else if (j < es) {
+        const uint32_t q = Q[j - e];
+        if (ir >= 0)
+          for (uint32_t t = 0; t < e; t++) c ^= gf_mul_d(G[q * k + E[t]], A[t][e + ir], exp, log);
+        else if (r == q)
+          c = 1u;  // s_q itself
+      }
+      uint32_t poly = 0;
+      for (int b = 0; b < 16; b++) poly ^= (c >> b & 1u) ? cantor[b] : 0u;
+      pl[nw + 3 + r * m + j] = poly;
+    }
+  }
+  for (uint32_t i = 0; i < e; i++) pl[E[i] / 32] |= 1u << (E[i] % 32);
+  pl[nw] = rm;
+  pl[nw + 1] = es < max_e ? es : max_e;
+  pl[nw + 2] = rm | qm;
+}
+
 // Per-stripe plan of the wide-code path (rs_psyn.hpp solve kernel after the FFT
 // syndrome kernel, chunk 32 / 64): as k_psyn_plan for any e <= m <= 64, one thread per
 // stripe (the e x 2e Gauss-Jordan lives in private memory). Block per stripe (u32):
@@ -650,6 +735,18 @@ hipError_t launch_psyn_plan(const uint8_t *present, uint64_t present_stride, uin
   trace_launch("k_psyn_plan");
   hipLaunchKernelGGL(k_psyn_plan, dim3(static_cast<uint32_t>((n + 63) / 64)), dim3(64), 0, s, present, present_stride,
                      k, m, max_out, max_e, n, G, d_exp, d_log, plan, plan_dw, status);
+  return hipGetLastError();
+}
+
+hipError_t launch_psyn_rebuild_plan(const uint8_t *present, uint64_t present_stride, uint32_t k, uint32_t m,
+                                    uint32_t max_e, uint64_t n, const uint16_t *G, const uint16_t *d_exp,
+                                    const uint16_t *d_log, uint32_t *plan, uint32_t plan_dw, int32_t *status,
+                                    hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  if (k > 256 || m > kPsynMaxM || plan_dw < (k + 31) / 32 + 3 + m * m) return hipErrorInvalidValue;
+  trace_launch("k_psyn_rebuild_plan");
+  hipLaunchKernelGGL(k_psyn_rebuild_plan, dim3(static_cast<uint32_t>((n + 63) / 64)), dim3(64), 0, s, present,
+                     present_stride, k, m, max_e, n, G, d_exp, d_log, plan, plan_dw, status);
   return hipGetLastError();
 }
 

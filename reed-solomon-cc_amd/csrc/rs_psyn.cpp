@@ -33,6 +33,7 @@ std::string key_of(const Spec &s) {
                   ":" + std::to_string(s.m) + ":" + std::to_string(s.flags) + ":";
   k.append(reinterpret_cast<const char *>(s.images.data()), s.images.size() * sizeof(uint16_t));
   k.append(reinterpret_cast<const char *>(s.cantor.data()), s.cantor.size() * sizeof(uint16_t));
+  if (s.rebuild) k += ":rebuild1";  // the reconstruct's key (and its on-disk cache entries) stay as they were
   return k;
 }
 
@@ -40,7 +41,8 @@ std::string name_of(const Spec &s) {
   uint64_t h = 1469598103934665603ull;
   for (unsigned char c : key_of(s)) h = (h ^ c) * 1099511628211ull;
   char name[96];
-  std::snprintf(name, sizeof name, "rs_psyn_reconstruct_k%u_m%u_%016llx", s.k, s.m, static_cast<unsigned long long>(h));
+  std::snprintf(name, sizeof name, "rs_psyn_%s_k%u_m%u_%016llx", s.rebuild ? "rebuild" : "reconstruct", s.k, s.m,
+                static_cast<unsigned long long>(h));
   return name;
 }
 
@@ -85,7 +87,11 @@ void emit_chain(std::ostringstream &o, uint32_t j) {
 }  // namespace
 
 std::string generate(const Spec &s, const std::string &name) {
-  const uint32_t K = s.k, M = s.m, MO = max_out(s.k, s.m), PDW = plan_dwords(s.k, s.m), NW = mask_words(s.k);
+  const uint32_t K = s.k, M = s.m, NW = mask_words(s.k);
+  // rebuild: m outputs (originals, then recovery shards), one more header word (the rows used)
+  const uint32_t MO = s.rebuild ? M : max_out(s.k, s.m), PDW = s.rebuild ? rebuild_plan_dwords(K, M) : plan_dwords(K, M);
+  const uint32_t CF0 = NW + (s.rebuild ? 3 : 2);  // the first coefficient word
+  const char *use = s.rebuild ? "um" : "rm";     // the mask of the rows the solve reads
   std::ostringstream o;
   // non-temporal loads and stores (every byte is touched once)
   o << "#define RS_NT 3\n" << jit::net_prelude();
@@ -109,6 +115,7 @@ std::string generate(const Spec &s, const std::string &name) {
     << "  const u32 ne = pl[" << NW + 1 << "];\n"
        "  if (ne == 0u) return;\n"
     << "  const u32 rm = pl[" << NW << "], sbl = (u32)sb;\n";
+  if (s.rebuild) o << "  const u32 um = pl[" << NW + 2 << "];\n";
   for (uint32_t w = 0; w < NW; w++) o << "  const u32 em" << w << " = pl[" << w << "];\n";
   o <<
        "  const u32 off = (u32)unit * 4096u + (ll >> 1) * 64u + (lane >= 32u ? 32u : 0u) + (ll & 1u) * 16u;\n"
@@ -208,16 +215,19 @@ std::string generate(const Spec &s, const std::string &name) {
     for (int c = 0; c < 16; c++) o << "z" << c << (c == 15 ? "};\n" : ", ");
     o << "  st(O + " << j << "ull * sb + off, Q);\n  }\n";
   };
-  if (M <= 4) {  // every output accumulates at once (16 MO + 16 M VGPRs)
+  // rebuild, m = 4 beside k < 8: the all-at-once shape spills 3 VGPRs under the 3-wave cap (the short
+  // network leaves the compiler less to overlap the 128 accumulators with), so one at a time
+  const bool at_once = M <= 4 && !(s.rebuild && M == 4 && K < 8);
+  if (at_once) {  // every output accumulates at once (16 MO + 16 M VGPRs)
     o << "  u32 ";
     for (uint32_t j = 0; j < MO; j++)
       for (int c = 0; c < 16; c++) o << "x" << j << "_" << c << " = 0u" << (j + 1 == MO && c == 15 ? ";\n" : ", ");
     for (uint32_t r = 0; r < M; r++) {
-      o << "  if ((rm >> " << r << ") & 1u) {\n";
+      o << "  if ((" << use << " >> " << r << ") & 1u) {\n";
       for (uint32_t j = 0; j < MO; j++) {
         // one chain per (r, j): branches on one coefficient only (branches on several
         // correlated conditions let the compiler thread and duplicate blocks)
-        o << "  if (" << j << "u < ne) {\n  const u32 cf = pl[" << NW + 2 + r * MO + j << "];\n  u32 ";
+        o << "  if (" << j << "u < ne) {\n  const u32 cf = pl[" << CF0 + r * MO + j << "];\n  u32 ";
         for (int c = 0; c < 16; c++) o << "X" << c << " = a" << r * 16 + c << (c == 15 ? ";\n" : ", ");
         emit_chain(o, j);
         o << "  }\n";
@@ -233,7 +243,7 @@ std::string generate(const Spec &s, const std::string &name) {
       o << "  if (" << j << "u < ne) {\n  u32 ";
       for (int c = 0; c < 16; c++) o << "x" << j << "_" << c << " = 0u" << (c == 15 ? ";\n" : ", ");
       for (uint32_t r = 0; r < M; r++) {
-        o << "  if ((rm >> " << r << ") & 1u) {\n  const u32 cf = pl[" << NW + 2 + r * MO + j << "];\n  u32 ";
+        o << "  if ((" << use << " >> " << r << ") & 1u) {\n  const u32 cf = pl[" << CF0 + r * MO + j << "];\n  u32 ";
         for (int c = 0; c < 16; c++) o << "X" << c << " = a" << r * 16 + c << (c == 15 ? ";\n" : ", ");
         emit_chain(o, j);
         o << "  }\n";

@@ -41,6 +41,11 @@ struct Spec {
   uint32_t k = 0, m = 0, flags = 0;
   std::vector<uint16_t> images;  // encode map: images[(t * m + r) * 16 + b] (rs_jit NetSpec layout)
   std::vector<uint16_t> cantor;  // the 16 Cantor basis elements in polynomial form (rs_gf.hpp)
+  // rs_rebuild_batch_dev: m outputs, lost recovery shards among them. The rows
+  // whose p_r is loaded (rm) and the rows the solve uses (um, one more plan word) differ: a lost
+  // row q is read as zero, so its syndrome is Enc_q of the received data, and the solve adds the
+  // erased originals' share to it. Plan block: rebuild_plan_dwords, built by k_psyn_rebuild_plan.
+  bool rebuild = false;
 };
 
 // restored outputs a kernel computes per stripe (the plan's max_out)
@@ -49,6 +54,9 @@ inline uint32_t max_out(uint32_t k, uint32_t m) { return k < m ? k : m; }
 // erased-original mask words, the R row mask, the outputs restored, then the coefficients
 inline uint32_t mask_words(uint32_t k) { return (k + 31) / 32; }
 inline uint32_t plan_dwords(uint32_t k, uint32_t m) { return mask_words(k) + 2 + m * max_out(k, m); }
+
+// the rebuild variant: mask words, R, the outputs stored, the rows used, then m x m coefficients
+inline uint32_t rebuild_plan_dwords(uint32_t k, uint32_t m) { return mask_words(k) + 3 + m * m; }
 
 bool supports(uint64_t k, uint64_t m, uint64_t shard_bytes);
 std::string generate(const Spec &s, const std::string &name);

@@ -8,7 +8,7 @@ after the Zig error set. Everything is computed by the gfx950 HIP kernels of
 fallback — without the library or a gfx950 device every call raises.
 
 Device batch API (``encode_batch_dev`` / ``reconstruct_batch_dev`` / ``verify_batch_dev`` /
-``locate_batch_dev`` / ``update_batch_dev``) takes
+``locate_batch_dev`` / ``update_batch_dev`` / ``rebuild_batch_dev``) takes
 torch tensors that already live in HBM (PyTorch is only the allocator and
 stream provider here).
 """
@@ -95,6 +95,10 @@ def lib():
         "rs_locate_selftest": (C.c_int, [u64, u64, C.c_int, u64, vp]),
         "rs_update_batch_dev": (C.c_int, [u64, u64, sz, u64, u32, vp, u64, vp, vp, u64, vp, u64, vp, u32, vp]),
         "rs_update_selftest": (C.c_int, [u64, u64, u32, C.c_int, u64, vp]),
+        "rs_rebuild_batch_dev": (C.c_int, [u64, u64, sz, u64, vp, u64, u32, vp, u64, vp, u64, vp, u64, vp, u32, vp]),
+        "rs_rebuild_kernel_name": (C.c_char_p, [u64, u64, sz, u32]),
+        "rs_rebuild_compile_check": (C.c_int, [u64, u64, vp, vp]),
+        "rs_rebuild_selftest": (C.c_int, [u64, u64, C.c_int, u64, vp]),
         "rs_encode_batch_host": (C.c_int, [u64, u64, sz, u64, vp, u64, vp, u64, u32]),
         "rs_reconstruct_batch_host": (C.c_int, [u64, u64, sz, u64, vp, vp, u64, vp, u64, vp, u64, u32]),
         "rs_encode_batch_host_multi": (C.c_int, [u64, u64, sz, u64, vp, u64, vp, u64, u32, vp, C.c_int]),
@@ -397,6 +401,56 @@ def update_selftest(k, m, max_u=4, trials=8, seed=1) -> int:
     """Host check of the update algebra (stored ^ sum c * delta == encode(new)): wrong symbols."""
     bad = C.c_uint64()
     _check(lib().rs_update_selftest(k, m, max_u, trials, seed, C.byref(bad)))
+    return bad.value
+
+
+def rebuild_batch_dev(original_count: int, recovery_count: int, present, original, recovery, rebuilt, status=None,
+                      stream=None):
+    """Every lost shard of a stripe comes back, recovery shards included. present: uint8 CUDA
+    tensor [n, k + m] (its row stride may exceed k + m; locate_batch_dev's rows as they are);
+    original [n, k, sb], recovery [n, m, sb], rebuilt [n, max_e, sb]: uint8 CUDA tensors with any
+    stripe stride (last two dimensions contiguous). Slots [0, e_o) of a stripe's row of rebuilt
+    receive its missing originals, ascending, slots [e_o, e_s) its missing recovery shards; the
+    others are not written. status: optional int32 CUDA tensor [n] (allocated when None): 0, 2
+    (fewer than k present: nothing written) or 14 (e_s > max_e: the first max_e slots are
+    written). Always the corrected arithmetic (flags 0, include/reedsol.h). Asynchronous on `stream`;
+    returns status."""
+    n, k, sb = original.shape
+    m = recovery_count
+    assert k == original_count and original.is_cuda and recovery.is_cuda and recovery.shape == (n, m, sb)
+    assert rebuilt.is_cuda and rebuilt.dim() == 3 and rebuilt.shape[0] == n and rebuilt.shape[2] == sb
+    max_e = rebuilt.shape[1]
+    assert present.is_cuda and present.element_size() == 1 and present.shape == (n, k + m)
+    assert n == 0 or (original[0].is_contiguous() and recovery[0].is_contiguous() and present[0].is_contiguous())
+    assert n == 0 or max_e == 0 or rebuilt[0].is_contiguous()
+    if status is None:
+        import torch
+        status = torch.empty((n,), dtype=torch.int32, device=original.device)
+    assert status.is_cuda and status.shape == (n,) and status.is_contiguous()
+    _check(lib().rs_rebuild_batch_dev(
+        k, m, sb, n, C.c_void_p(present.data_ptr()), present.stride(0), max_e,
+        C.c_void_p(original.data_ptr()), original.stride(0), C.c_void_p(recovery.data_ptr()), recovery.stride(0),
+        C.c_void_p(rebuilt.data_ptr()), rebuilt.stride(0), C.c_void_p(status.data_ptr()), FLAG_CORRECTED,
+        _stream_handle(stream)))
+    return status
+
+
+def rebuild_kernel_name(k, m, shard_bytes, max_e) -> str:
+    """Path of rebuild_batch_dev for these arguments (include/reedsol.h)."""
+    return lib().rs_rebuild_kernel_name(k, m, shard_bytes, max_e).decode()
+
+
+def rebuild_compile_check(k, m) -> dict:
+    """Generate and compile the rebuild variant of the code's syndrome network (no device)."""
+    ms, b = C.c_double(), C.c_uint64()
+    _check(lib().rs_rebuild_compile_check(k, m, C.byref(ms), C.byref(b)))
+    return {"compile_ms": ms.value, "code_bytes": b.value}
+
+
+def rebuild_selftest(k, m, trials=8, seed=1) -> int:
+    """Host check of the rebuild algebra (the plan kernel's coefficients on scalar symbols): wrong symbols."""
+    bad = C.c_uint64()
+    _check(lib().rs_rebuild_selftest(k, m, trials, seed, C.byref(bad)))
     return bad.value
 
 
