@@ -206,7 +206,8 @@ const char *rs_verify_kernel_name(uint64_t original_count, uint64_t recovery_cou
  * corrupt shards and m >= 3 no stripe is reported as a single shard (a weight-2 and a weight-1
  * error with equal syndromes would differ by a codeword of weight <= 3 < m + 1). With m == 2 two
  * corrupt shards can imitate one: the code's limit. m == 1: a disagreeing stripe is
- * RS_LOCATE_UNLOCATED. Locating more than one corrupt shard is out of scope.
+ * RS_LOCATE_UNLOCATED. Locating more than one corrupt shard is rs_locate_multi_batch_dev's job
+ * (below).
  * Accepts everything rs_verify_batch_dev accepts, validated in the same order and with the same
  * alignment contract (any even shard_bytes, d_original and its stride 4-byte aligned when
  * shard_bytes % 64 == 0, d_recovery at any alignment, low-rate codes, strides; n_stripes == 0:
@@ -236,6 +237,71 @@ const char *rs_locate_kernel_name(uint64_t original_count, uint64_t recovery_cou
  * original_count == 0. */
 int rs_locate_selftest(uint64_t original_count, uint64_t recovery_count, int trials, uint64_t seed,
                        uint64_t *mismatches);
+
+/* Locate, several shards: for every stripe, name the up to max_t shards whose corruption explains
+ * every disagreement, originals and recovery shards alike. With flags == 0 let G = [C | I_m], an
+ * m x (k + m) matrix over GF(2^16): column j < k holds the encode's coefficients c[r][j], column
+ * k + r the unit vector e_r (a corrupt recovery shard r disturbs only S_r). With corrupt shards T
+ * the syndrome vector of symbol p is S(p) = sum_{i in T} G_i * err_i(p). Every symbol of a stripe
+ * shares T, so the S(p) span a subspace V of dimension rho <= |T|; the code being MDS, any m columns
+ * of G are independent, and the columns of G that lie in V are corrupt shards. The rank is found
+ * by the pass that confirms it: a basis of V in reduced form grows by one vector per round, taken
+ * at the first symbol the previous round found outside the span.
+ * max_t: 1 .. min(recovery_count / 2, RS_LOCATE_MAX_T).
+ * d_count (device, n_stripes int32, every one written): 0 for a clean stripe, t in [1, max_t] for
+ * t located shards, or RS_LOCATE_UNLOCATED. RS_LOCATE_RECOVERY_SET is never returned: bad recovery
+ * shards are named like any others.
+ * d_located (device, optional): n_stripes rows of max_t int32 (row stride located_stride, in
+ * words, 0 = max_t; words between rows are not touched): slots [0, t) hold the located shards'
+ * indices in [0, k + m), ascending, originals first as in `present`; every other slot of the row
+ * holds -1 (all of them for a clean or unlocated stripe).
+ * d_present (device, optional): n_stripes rows of k + m flags (row stride present_stride, 0 =
+ * k + m; bytes between rows are not touched): 0 at each located shard, 1 elsewhere; all 1 for
+ * clean and unlocated stripes. A row can be passed as it is to rs_rebuild_batch_dev with
+ * max_e = max_t.
+ * d_counts (device, optional): max_t + 2 words, the stripes with 0, 1, .., max_t located shards,
+ * then the unlocated ones. No input is written.
+ * Guarantee, for max_t <= m / 2: a stripe with at most m / 2 corrupt shards is never given a wrong
+ * answer. Its T is reported exactly if |T| <= max_t and the errors of its shards are linearly
+ * independent as rows over the symbol positions (any real corruption, with overwhelming
+ * probability); it is RS_LOCATE_UNLOCATED if the rank exceeds max_t, or if the errors are
+ * rank-deficient (err_b = alpha * err_a at every symbol, or fewer distinct corrupt symbol positions
+ * than shards): then fewer than rho columns lie in V and nothing is named. More than m / 2 corrupt
+ * shards are beyond unique decoding: such a stripe is unlocated whenever its rank exceeds max_t, and
+ * may otherwise imitate a smaller set. Out of scope: more than RS_LOCATE_MAX_T shards,
+ * probabilistic location beyond m / 2, known erasures combined with errors, a *_host form, the
+ * quirk flags.
+ * Validated on the host before any device call, in rs_locate_batch_dev's order and with its
+ * alignment contract (original_count == 0, the encode's checks, n_stripes == 0: RS_OK and nothing
+ * written, NULL pointers and strides below the row size, flags != 0, d_original and its stride
+ * 4-byte aligned when shard_bytes % 64 == 0), then RS_ERR_INVALID_ARGUMENT for a NULL d_count,
+ * max_t == 0 or above min(recovery_count / 2, RS_LOCATE_MAX_T) (so recovery_count < 2 is always
+ * invalid), 0 < located_stride < max_t, 0 < present_stride < k + m.
+ * Slices of stripes (scratch at most RS_AMD_SCRATCH_CAP_MB: the encode's m rows, 98 * max_t * m
+ * bytes of basis and multiply tables and m + 16 + 8 * max_t bytes of state per stripe) are encoded
+ * and compared as by rs_verify_batch_dev, whose flags settle clean stripes; then max_t + 1 rounds of
+ * k_mloc_check (16-byte, dword or byte loads as rs_last_kernels reports: _x16 / _x4 / _x1) and
+ * k_mloc_extend, k_mloc_match and k_mloc_finish run without host synchronisation. A stripe with t
+ * corrupt shards is read t + 1 more times, 2m rows each (round 0 reads only the rows whose compare
+ * flag is set). */
+#define RS_LOCATE_MAX_T 8
+int rs_locate_multi_batch_dev(uint64_t original_count, uint64_t recovery_count, size_t shard_bytes,
+                              uint64_t n_stripes, uint32_t max_t, const void *d_original,
+                              uint64_t original_stripe_stride, const void *d_recovery,
+                              uint64_t recovery_stripe_stride, int32_t *d_count, int32_t *d_located,
+                              uint64_t located_stride, uint8_t *d_present, uint64_t present_stride,
+                              uint64_t *d_counts, uint32_t flags, rs_stream_t stream);
+/* The path it takes: "<rs_encode_kernel_name>+verify_compare+locate_multi_t<max_t>". */
+const char *rs_locate_multi_kernel_name(uint64_t original_count, uint64_t recovery_count, size_t shard_bytes,
+                                        uint32_t max_t);
+/* Host check of the algebra above (no device), on 12 symbols per shard: over `trials` random
+ * stripes, every t in 0 .. max_t corrupt shards (random mixes of originals and recovery shards,
+ * errors of full rank) must be located exactly; max_t + 1 shards, each wrong at a symbol of its
+ * own, and with recovery_count >= 4 a pair with proportional errors must be RS_LOCATE_UNLOCATED.
+ * *mismatches = wrong answers (or 1 for a zero coefficient). RS_ERR_INVALID_ARGUMENT for
+ * original_count == 0 or a max_t the batch call rejects. */
+int rs_locate_multi_selftest(uint64_t original_count, uint64_t recovery_count, uint32_t max_t, int trials,
+                             uint64_t seed, uint64_t *mismatches);
 
 /* Update (the small write): some originals of a stripe change and its stored recovery shards
  * follow in place, without the other originals. With flags == 0 the encode is linear over

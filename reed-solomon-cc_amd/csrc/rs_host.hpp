@@ -1,12 +1,12 @@
 // rs_host.hpp — internal interface of the host codec (librs_amd.so): validation and
 // error reporting, plan caches, kernel selection, plans, and the entry points the
 // C ABI files (rs_batch_dev.cpp, rs_patterns.cpp, rs_lowrate.cpp, rs_host_batch.cpp,
-// rs_oneshot.cpp, rs_verify.cpp, rs_locate.cpp, rs_update.cpp, rs_rebuild.cpp) share: the stream-ordered scratch
+// rs_oneshot.cpp, rs_verify.cpp, rs_locate.cpp, rs_locate_multi.cpp, rs_update.cpp, rs_rebuild.cpp) share: the stream-ordered scratch
 // (StreamScratch, the only place that frees one) and the slice loop over it (in_scratch_slices,
 // sized by rs_slices.hpp), the shard-tail helpers, and the shell of the scrub family (argument
 // front, encode-and-compare step, CodePlan). Host-side mirror of root.zig's checks and error
 // precedence; every device computation runs in the precompiled kernels
-// (rs_kernels.hip, rs_phase_kernels.hip, rs_plan_kernels.hip, rs_locate_kernels.hip, rs_update_kernels.hip,
+// (rs_kernels.hip, rs_phase_kernels.hip, rs_plan_kernels.hip, rs_locate_kernels.hip, rs_locate_multi_kernels.hip, rs_update_kernels.hip,
 // rs_rebuild_kernels.hip) or in a hipRTC kernel (rs_jit / rs_fftnet / rs_psyn); there is no CPU compute path.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -60,7 +60,7 @@ void release_plans();      // rs_plans.cpp (+ twiddles, rs_common.cpp)
 void release_patterns();   // rs_patterns.cpp
 void release_lowrate();    // rs_lowrate.cpp
 void release_oneshot();    // rs_oneshot.cpp
-void release_code_plans(); // rs_verify.cpp: the locate and update plans
+void release_code_plans(); // rs_verify.cpp: the locate, multi-locate and update plans
 size_t oneshot_pooled();   // one-shot contexts idle in the pool
 void release_host_rings(); // rs_host_batch.cpp
 
@@ -345,12 +345,13 @@ int check_scrub_args(uint64_t k, uint64_t m, size_t sb, uint64_t n, const void *
 int encode_and_compare(uint64_t k, uint64_t m, uint64_t sb, uint64_t cnt, const uint8_t *orig, uint64_t ostride,
                        uint8_t *scratch, const uint8_t *rec, uint64_t rstride, uint8_t *bad, uint64_t bad_stride,
                        uint32_t flags, hipStream_t s);
-// Per (device, k, m): one blob of uint16 in HBM (locate: ratio logs; update: coefficient logs)
+// Per (device, k, m): one blob of uint16 in HBM (locate: ratio logs; update and the multi-shard
+// locate: coefficient logs, each in its own cache)
 struct CodePlan {
   std::shared_ptr<DevBuf> buf;
   const uint16_t *u16() const { return static_cast<const uint16_t *>(buf->p); }
 };
-extern PlanCache<CodePlan> g_locate_plans, g_update_plans;
+extern PlanCache<CodePlan> g_locate_plans, g_locate_multi_plans, g_update_plans;
 // the cached plan, or build(blob) uploaded; build fails with its own message (fail())
 int get_code_plan(PlanCache<CodePlan> &cache, int dev, uint64_t k, uint64_t m,
                   const std::function<int(std::vector<uint16_t> &)> &build, std::shared_ptr<CodePlan> &out);
@@ -429,7 +430,7 @@ int psyn_rebuild(int dev, uint64_t k, uint64_t m, uint64_t sb, uint64_t n, const
 // cl[j * m + r] = log c[r][j] in [0, 65535), the encode's coefficients (parity[r] = sum_j c[r][j]
 // * original[j] under the corrected arithmetic), from the scalar encode of unit vectors (the
 // low-rate encode for low-rate codes). false if a coefficient is zero (never in an MDS code).
-// rs_update.cpp; locate derives its ratios from it.
+// rs_update.cpp; locate derives its ratios from it, the multi-shard locate matches columns with it.
 bool coef_logs(uint64_t k, uint64_t m, std::vector<uint16_t> &cl);
 // exp, log, log_walsh in HBM (384 KiB per device)
 int device_tables(int dev, const uint16_t **exp, const uint16_t **log, const uint16_t **lw);

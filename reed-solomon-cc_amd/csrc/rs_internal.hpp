@@ -1,6 +1,6 @@
 // rs_internal.hpp — launch interface between the host codec (rs_host.hpp and the files behind it) and
 // the HIP kernels (rs_kernels.hip, rs_phase_kernels.hip, rs_plan_kernels.hip, rs_locate_kernels.hip,
-// rs_update_kernels.hip, rs_rebuild_kernels.hip). Not part of the public ABI.
+// rs_locate_multi_kernels.hip, rs_update_kernels.hip, rs_rebuild_kernels.hip). Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -267,6 +267,39 @@ hipError_t launch_locate_confirm(const uint8_t *enc, uint64_t enc_stride, const 
 hipError_t launch_locate_finish(const int32_t *cls, const uint8_t *bad, const uint8_t *reject, uint32_t k, uint32_t m,
                                 uint64_t n, int32_t *located, uint8_t *present, uint64_t present_stride,
                                 uint64_t *counts, hipStream_t s);
+
+// Locate, up to max_t shards (rs_locate_multi.cpp, rs_locate_multi_kernels.hip): enc, rec and bad
+// as above. Per stripe of a slice: state (kMlocActive while rounds run — what a memset to 0xFF
+// leaves —, then the rank of the syndromes' span or kLocUnlocated), pos (the smallest symbol index
+// outside the span, kMlocNoPos: none; 0xFF bytes too), the basis [max_t][m] as symbols, its pivot
+// rows piv [max_t] and the multiply tables tabs [max_t][m] of its entries.
+constexpr uint32_t kMlocMaxT = 8;  // RS_LOCATE_MAX_T
+constexpr int32_t kMlocActive = -1;
+constexpr unsigned long long kMlocNoPos = ~0ull;
+// round `round` <= max_t <= kMlocMaxT of the check: pos[s] = min over the symbols that do not lie
+// in the span of the first `round` basis vectors. The launch record names the load width
+// (k_mloc_check_x16 / _x4 / _x1).
+hipError_t launch_mloc_check(const uint8_t *enc, uint64_t enc_stride, const uint8_t *rec, uint64_t rec_stride,
+                             uint64_t sb, uint64_t n, uint32_t m, uint32_t round, uint32_t max_t, const int32_t *state,
+                             const uint8_t *bad, const uint32_t *piv, const RsTab *tabs, uint64_t *pos,
+                             hipStream_t s);
+// settles the stripes whose check found nothing (rank `round`) or that need a vector past max_t
+// (kLocUnlocated); the others get basis vector `round`, their tables rebuilt and pos reset
+hipError_t launch_mloc_extend(const uint8_t *enc, uint64_t enc_stride, const uint8_t *rec, uint64_t rec_stride,
+                              uint64_t sb, uint64_t n, uint32_t m, uint32_t round, uint32_t max_t,
+                              const uint16_t *d_exp, const uint16_t *d_log, int32_t *state, uint64_t *pos,
+                              uint32_t *piv, uint16_t *basis, RsTab *tabs, hipStream_t s);
+// found [n][max_t], nfound [n]: the columns of G = [C | I] in each settled stripe's span, ascending
+// (cl [k][m] = the plan's log c[r][j])
+hipError_t launch_mloc_match(uint64_t n, uint32_t k, uint32_t m, uint32_t max_t, const uint16_t *cl,
+                             const uint16_t *d_exp, const uint16_t *d_log, const int32_t *state, const uint32_t *piv,
+                             const uint16_t *basis, int32_t *found, uint32_t *nfound, hipStream_t s);
+// count [n], located rows (may be NULL), present rows (may be NULL) and counts[max_t + 2] (may be
+// NULL; added to, zeroed by the caller)
+hipError_t launch_mloc_finish(const int32_t *state, const int32_t *found, const uint32_t *nfound, uint32_t k,
+                              uint32_t m, uint32_t max_t, uint64_t n, int32_t *count, int32_t *located,
+                              uint64_t located_stride, uint8_t *present, uint64_t present_stride, uint64_t *counts,
+                              hipStream_t s);
 
 // Update (rs_update.cpp, rs_update_kernels.hip): index rows [n][max_u] of changed originals
 // (kUpdateNone = RS_UPDATE_NONE: an empty slot), cl [k][m] = the plan's log c[r][j]. Per stripe:

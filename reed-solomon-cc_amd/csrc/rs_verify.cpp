@@ -3,7 +3,7 @@
 // rs_encode_batch_dev itself, then k_verify_compare (rs_kernels.hip) compares the scratch with
 // the stored shards and k_verify_count sums the flags. Also the shell the scrub
 // family shares (rs_host.hpp): the argument front and the encode-and-compare step of verify and
-// locate, and the per-code plans of locate and update.
+// locate, and the per-code plans of locate, the multi-shard locate and update.
 #include "rs_host.hpp"
 
 namespace rs {
@@ -31,7 +31,7 @@ int encode_and_compare(uint64_t k, uint64_t m, uint64_t sb, uint64_t cnt, const 
                     "launch_verify_compare");
 }
 
-PlanCache<CodePlan> g_locate_plans, g_update_plans;
+PlanCache<CodePlan> g_locate_plans, g_locate_multi_plans, g_update_plans;
 
 int get_code_plan(PlanCache<CodePlan> &cache, int dev, uint64_t k, uint64_t m,
                   const std::function<int(std::vector<uint16_t> &)> &build, std::shared_ptr<CodePlan> &out) {
@@ -53,6 +53,7 @@ int get_code_plan(PlanCache<CodePlan> &cache, int dev, uint64_t k, uint64_t m,
 void release_code_plans() {
   std::lock_guard<std::mutex> lk(g_plan_mu);
   g_locate_plans.clear();
+  g_locate_multi_plans.clear();
   g_update_plans.clear();
 }
 

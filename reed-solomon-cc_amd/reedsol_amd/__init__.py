@@ -8,7 +8,7 @@ after the Zig error set. Everything is computed by the gfx950 HIP kernels of
 fallback — without the library or a gfx950 device every call raises.
 
 Device batch API (``encode_batch_dev`` / ``reconstruct_batch_dev`` / ``verify_batch_dev`` /
-``locate_batch_dev`` / ``update_batch_dev`` / ``rebuild_batch_dev``) takes
+``locate_batch_dev`` / ``locate_multi_batch_dev`` / ``update_batch_dev`` / ``rebuild_batch_dev``) takes
 torch tensors that already live in HBM (PyTorch is only the allocator and
 stream provider here).
 """
@@ -30,6 +30,8 @@ FLAG_REF_LITERAL = 3
 LOCATE_CLEAN = -1
 LOCATE_RECOVERY_SET = -2
 LOCATE_UNLOCATED = -3
+# the most shards locate_multi_batch_dev names in a stripe (include/reedsol.h RS_LOCATE_MAX_T)
+LOCATE_MAX_T = 8
 
 # an empty slot of update_batch_dev's index rows (include/reedsol.h RS_UPDATE_NONE)
 UPDATE_NONE = 0xFFFFFFFF
@@ -93,6 +95,10 @@ def lib():
         "rs_locate_batch_dev": (C.c_int, [u64, u64, sz, u64, vp, u64, vp, u64, vp, vp, u64, vp, u32, vp]),
         "rs_locate_kernel_name": (C.c_char_p, [u64, u64, sz]),
         "rs_locate_selftest": (C.c_int, [u64, u64, C.c_int, u64, vp]),
+        "rs_locate_multi_batch_dev": (C.c_int, [u64, u64, sz, u64, u32, vp, u64, vp, u64, vp, vp, u64, vp, u64, vp, u32,
+                                                vp]),
+        "rs_locate_multi_kernel_name": (C.c_char_p, [u64, u64, sz, u32]),
+        "rs_locate_multi_selftest": (C.c_int, [u64, u64, u32, C.c_int, u64, vp]),
         "rs_update_batch_dev": (C.c_int, [u64, u64, sz, u64, u32, vp, u64, vp, vp, u64, vp, u64, vp, u32, vp]),
         "rs_update_selftest": (C.c_int, [u64, u64, u32, C.c_int, u64, vp]),
         "rs_rebuild_batch_dev": (C.c_int, [u64, u64, sz, u64, vp, u64, u32, vp, u64, vp, u64, vp, u64, vp, u32, vp]),
@@ -360,6 +366,57 @@ def locate_selftest(k, m, trials=8, seed=1) -> int:
     """Host check of the locate algebra (distinct ratios, every outcome): wrong answers."""
     bad = C.c_uint64()
     _check(lib().rs_locate_selftest(k, m, trials, seed, C.byref(bad)))
+    return bad.value
+
+
+def locate_multi_batch_dev(original_count: int, recovery_count: int, original, recovery, max_t: int, count=None,
+                           located=None, present=None, counts=None, stream=None):
+    """Name up to max_t corrupt shards per stripe (1 <= max_t <= min(m // 2, LOCATE_MAX_T)):
+    original [n, k, sb] and stored recovery [n, m, sb] (uint8 CUDA tensors, last two dimensions
+    contiguous) -> count, a torch.int32 tensor [n] (allocated when None): 0 for a clean stripe, t
+    for t located shards, or LOCATE_UNLOCATED. located: optional int32 CUDA tensor [n, max_t] (its
+    row stride may exceed max_t): the located indices in [0, k + m), ascending, then -1. present:
+    optional uint8 CUDA tensor [n, k + m] (its row stride may exceed k + m): 0 at each located
+    shard, the rows rebuild_batch_dev takes. counts: optional int64 CUDA tensor of max_t + 2
+    elements: the stripes with 0 .. max_t located shards, then the unlocated ones. Always the
+    corrected arithmetic (flags 0, include/reedsol.h). Asynchronous on `stream`; returns count."""
+    n, k, sb = original.shape
+    m = recovery_count
+    assert k == original_count and recovery.shape == (n, m, sb)
+    assert original.is_cuda and recovery.is_cuda
+    assert n == 0 or (original[0].is_contiguous() and recovery[0].is_contiguous())
+    if count is None:
+        import torch
+        count = torch.empty((n,), dtype=torch.int32, device=original.device)
+    assert count.is_cuda and count.shape == (n,) and count.is_contiguous() and count.element_size() == 4
+    if located is not None:
+        assert located.is_cuda and located.shape == (n, max_t) and located.element_size() == 4
+        assert n == 0 or located[0].is_contiguous()
+    if present is not None:
+        assert present.is_cuda and present.shape == (n, k + m) and (n == 0 or present[0].is_contiguous())
+    if counts is not None:
+        assert counts.is_cuda and counts.numel() == max_t + 2 and counts.element_size() == 8
+    _check(lib().rs_locate_multi_batch_dev(
+        k, m, sb, n, max_t, C.c_void_p(original.data_ptr()), original.stride(0),
+        C.c_void_p(recovery.data_ptr()), recovery.stride(0), C.c_void_p(count.data_ptr()),
+        C.c_void_p(located.data_ptr()) if located is not None else None,
+        located.stride(0) if located is not None else 0,
+        C.c_void_p(present.data_ptr()) if present is not None else None,
+        present.stride(0) if present is not None else 0,
+        C.c_void_p(counts.data_ptr()) if counts is not None else None, FLAG_CORRECTED, _stream_handle(stream)))
+    return count
+
+
+def locate_multi_kernel_name(k, m, shard_bytes, max_t) -> str:
+    """Path of locate_multi_batch_dev for these arguments (include/reedsol.h)."""
+    return lib().rs_locate_multi_kernel_name(k, m, shard_bytes, max_t).decode()
+
+
+def locate_multi_selftest(k, m, max_t, trials=8, seed=1) -> int:
+    """Host check of the multi-shard locate algebra (every t <= max_t located, rank-deficient
+    and rank > max_t stripes unlocated): wrong answers."""
+    bad = C.c_uint64()
+    _check(lib().rs_locate_multi_selftest(k, m, max_t, trials, seed, C.byref(bad)))
     return bad.value
 
 
