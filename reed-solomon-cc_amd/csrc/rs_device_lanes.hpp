@@ -1,7 +1,8 @@
 // rs_device_lanes.hpp — what the locate and the update kernels (rs_locate_kernels.hip,
-// rs_update_kernels.hip) share on the device: one lane's dword pairs of a shard in the chunk
-// layout at three access widths (16-byte vectors, dwords, bytes), the tail chunk by bytes, and the
-// multiply tables of a field element built from its log.
+// rs_locate_multi_kernels.hip, rs_update_kernels.hip) share on the device: one lane's dword pairs of
+// a shard in the chunk layout at three access widths (16-byte vectors, dwords, bytes), the tail
+// chunk by bytes, and the multiply tables of a field element built from its log. The pass over a
+// stripe's syndromes that the two locates run on these loads is rs_device_span.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

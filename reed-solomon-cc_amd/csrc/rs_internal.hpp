@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "rs_gf.hpp"
@@ -20,6 +22,24 @@ struct TraceScope {
   ~TraceScope();
 };
 const char *trace_text();
+
+// What the launchers of the width-templated kernels share (verify, locate, update). load_mode: the
+// widest access that every pointer, stride and size given allows: 2 = 16 bytes, 1 = dwords,
+// 0 = bytes. with_int: calls f(std::integral_constant<int, I>()) for the I of the list that equals
+// v (none: f is not called), so a run-time mode, tile or round picks a kernel instantiation:
+//   with_int(mode, kModes, [&](auto mc) { hipLaunchKernelGGL(kernel<decltype(mc)::value>, ...); });
+inline uint64_t align_bits(uint64_t v) { return v; }
+inline uint64_t align_bits(const void *p) { return reinterpret_cast<uint64_t>(p); }
+template <class... A>
+int load_mode(A... a) {
+  const uint64_t al = (align_bits(a) | ...);
+  return al % 16 == 0 ? 2 : al % 4 == 0 ? 1 : 0;
+}
+template <int... I, class F>
+void with_int(int v, std::integer_sequence<int, I...>, F &&f) {
+  (void)((v == I ? (f(std::integral_constant<int, I>()), true) : false) || ...);
+}
+constexpr std::integer_sequence<int, 2, 1, 0> kModes{};
 
 // Encode: data [stripe][k][sb] -> parity [stripe][m][sb].
 // Table block: n_chunks x ifft_tab_count(chunk) (chunk j has skew_delta (j+1)*chunk),

@@ -1266,17 +1266,10 @@ hipError_t launch_verify_compare(const uint8_t *a, uint64_t a_stripe_stride, con
   const uint64_t segs = (sb + kVerifySeg - 1) / kVerifySeg, total = n * m * segs;
   // grid-stride over the work items: the grid stays inside the launch limits for any batch
   const dim3 grid(static_cast<uint32_t>(std::min<uint64_t>(total, 1u << 20)));
-  const uint64_t al = reinterpret_cast<uint64_t>(a) | reinterpret_cast<uint64_t>(b) | a_stripe_stride |
-                      b_stripe_stride | sb;
-  if (al % 16 == 0)
-    hipLaunchKernelGGL(k_verify_compare<2>, grid, dim3(256), 0, s, a, a_stripe_stride, b, b_stripe_stride, sb, n, m,
-                       segs, bad, bad_stride);
-  else if (al % 4 == 0)
-    hipLaunchKernelGGL(k_verify_compare<1>, grid, dim3(256), 0, s, a, a_stripe_stride, b, b_stripe_stride, sb, n, m,
-                       segs, bad, bad_stride);
-  else
-    hipLaunchKernelGGL(k_verify_compare<0>, grid, dim3(256), 0, s, a, a_stripe_stride, b, b_stripe_stride, sb, n, m,
-                       segs, bad, bad_stride);
+  with_int(load_mode(a, a_stripe_stride, b, b_stripe_stride, sb), kModes, [&](auto mode) {
+    hipLaunchKernelGGL(k_verify_compare<decltype(mode)::value>, grid, dim3(256), 0, s, a, a_stripe_stride, b,
+                       b_stripe_stride, sb, n, m, segs, bad, bad_stride);
+  });
   return hipGetLastError();
 }
 

@@ -12,9 +12,9 @@
 //    belongs to, look log S_1 - log S_0 up among the code's k ratio logs (one j per lane), and
 //    build the candidate's m - 1 multiply tables c[r][j] / c[0][j] from their logs.
 //  * k_locate_confirm: flattened over (stripe, row group, 16 KiB segment), grid-stride; checks
-//    S_r == mul(S_0, c[r][j] / c[0][j]) on Sym<NV> registers with the v_perm multiply; a wave that
-//    sees a difference stores 1 to the stripe's reject byte. A stripe that is no candidate costs
-//    one load of its class per work item.
+//    S_r == mul(S_0, c[r][j] / c[0][j]) with dev::span_check (rs_device_span.hpp: one pivot row,
+//    row 0, rows from 1, no position wanted); a wave that sees a difference stores 1 to the
+//    stripe's reject byte. A stripe that is no candidate costs one load of its class per work item.
 //  * k_locate_finish: d_located, the d_present rows, d_counts.
 // A kernel boundary separates every producer from its consumers (no hand-off inside a kernel).
 #include <hip/hip_runtime.h>
@@ -23,19 +23,16 @@
 
 #include "rs_device.hpp"
 #include "rs_device_lanes.hpp"
+#include "rs_device_span.hpp"
 #include "rs_internal.hpp"
 
 namespace rs {
 namespace {
 
 using dev::build_tab;
-using dev::Lanes;
-using dev::ld_xor;
-using dev::ld_xor_tail;
-using dev::Sym;
-using dev::Tab;
+using dev::kRows;
+using dev::kSeg;
 
-constexpr uint32_t kLocateSeg = 16384;  // as k_verify_compare: a multiple of 16 and of 64
 constexpr uint32_t kNoLog = 0xFFFFFFFFu;
 
 // ============================================================ classify + candidate
@@ -85,8 +82,8 @@ __global__ __launch_bounds__(256) void k_locate_classify(
     // every row disagrees: a byte where S_0 is nonzero (the lowest offset of the first segment
     // that has one)
     const uint8_t *pa = enc + s * enc_stride, *pb = rec + s * rec_stride;
-    for (uint64_t base = 0; base < sb; base += kLocateSeg) {
-      const uint32_t len = static_cast<uint32_t>(sb - base < kLocateSeg ? sb - base : kLocateSeg);
+    for (uint64_t base = 0; base < sb; base += kSeg) {
+      const uint32_t len = static_cast<uint32_t>(sb - base < kSeg ? sb - base : kSeg);
       const uint8_t *qa = pa + base, *qb = pb + base;
       uint32_t at = 0xFFFFFFFFu;
       if (MODE == 2) {
@@ -123,15 +120,8 @@ __global__ __launch_bounds__(256) void k_locate_classify(
     }
     __syncthreads();
     if (tid == 0 && sh_pos != ~0ull) {
-      const uint64_t o = sh_pos, t = sb % 64, whole = sb - t, h = t / 2;
-      uint64_t lo, hi;  // the byte offsets of the symbol that byte o belongs to
-      if (o < whole) {
-        lo = o / 64 * 64 + o % 32;
-        hi = lo + 32;
-      } else {
-        lo = whole + (o - whole) % h;
-        hi = lo + h;
-      }
+      uint64_t lo, hi;  // the byte offsets of the symbol that byte sh_pos belongs to
+      dev::symbol_bytes(sb, dev::symbol_of(sb, sh_pos), lo, hi);
       const uint32_t s0 = static_cast<uint32_t>(pa[lo] ^ pb[lo]) | static_cast<uint32_t>(pa[hi] ^ pb[hi]) << 8;
       const uint32_t s1 = static_cast<uint32_t>(pa[sb + lo] ^ pb[sb + lo]) |
                           static_cast<uint32_t>(pa[sb + hi] ^ pb[sb + hi]) << 8;
@@ -152,77 +142,29 @@ __global__ __launch_bounds__(256) void k_locate_classify(
 }
 
 // ======================================================================= confirm
-// Work item = (stripe, group of up to kLocateRows rows r >= 1, segment). S_0 of the lane's unit
-// stays in registers while the group's rows pass; the table of (stripe, r) is wave-uniform.
-constexpr uint32_t kLocateRows = 16;
-
+// Work item = (stripe, group of up to kRows rows r >= 1, segment): dev::span_check with the one
+// pivot row 0, whose S_0 stays in registers while the group's rows pass; the table of (stripe, r)
+// is tabs[s][r - 1].
 template <int MODE>
 __global__ __launch_bounds__(256) void k_locate_confirm(const uint8_t *__restrict__ enc, uint64_t enc_stride,
                                                         const uint8_t *__restrict__ rec, uint64_t rec_stride,
                                                         uint64_t sb, uint64_t n, uint32_t k, uint32_t m, uint64_t segs,
                                                         uint32_t groups, const int32_t *__restrict__ cls,
                                                         const RsTab *__restrict__ tabs, uint8_t *reject) {
-  constexpr int NV = Lanes<MODE>::NV;
-  constexpr uint32_t kUnitsPerChunk = 8 / NV, kLo = 4 * NV;  // a unit: kLo low + kLo high bytes of one chunk
   const uint64_t per_stripe = segs * groups, total = n * per_stripe;
-  const uint32_t t = static_cast<uint32_t>(sb % 64);
-  const uint64_t whole = sb - t;
-  const uint32_t tid = threadIdx.x;
+  const uint32_t piv[1] = {0};
   for (uint64_t w = blockIdx.x; w < total; w += gridDim.x) {
     const uint64_t s = w / per_stripe, rem = w % per_stripe;
     const int32_t cand = cls[s];
     if (cand < 0 || static_cast<uint32_t>(cand) >= k) continue;  // no candidate: nothing to read
     if (*static_cast<volatile uint8_t *>(reject + s)) continue;  // already rejected (a stale 0 only costs time)
     const uint32_t g = static_cast<uint32_t>(rem / segs);
-    const uint64_t seg = rem % segs, base = seg * kLocateSeg;
-    const uint32_t r_lo = 1 + g * kLocateRows, r_hi = min(m, r_lo + kLocateRows);
-    const uint8_t *pa = enc + s * enc_stride + base, *pb = rec + s * rec_stride + base;
+    const uint32_t r_lo = 1 + g * kRows, r_hi = min(m, r_lo + kRows);
     const RsTab *tb = tabs + s * (m - 1);
-    const uint32_t wb = base < whole ? static_cast<uint32_t>(whole - base < kLocateSeg ? whole - base : kLocateSeg) : 0;
-    const uint32_t units = wb / 64 * kUnitsPerChunk;
-    uint32_t d = 0;
-    // the loop bounds are workgroup-uniform (a lane past the end re-reads unit 0 and drops the
-    // result), so the table loads stay scalar
-    for (uint32_t u0 = 0; u0 < units; u0 += 256u) {
-      const bool live = u0 + tid < units;
-      const uint32_t u = live ? u0 + tid : 0;
-      const uint32_t off = u / kUnitsPerChunk * 64 + u % kUnitsPerChunk * kLo;
-      Sym<NV> s0, sr;
-      ld_xor<MODE>(s0, pa + off, pb + off);
-      ld_xor<MODE>(sr, pa + r_lo * sb + off, pb + r_lo * sb + off);
-      uint32_t dd = 0;
-      for (uint32_t r = r_lo; r < r_hi; r++) {
-        Sym<NV> next = sr, pr;
-        // the next row's loads are in flight while this row is multiplied
-        if (r + 1 < r_hi) ld_xor<MODE>(next, pa + (r + 1) * sb + off, pb + (r + 1) * sb + off);
-        const Tab tab = dev::load_tab(tb + (r - 1));
-        dev::zero(pr);
-        dev::mul_add(pr, s0, tab);
-#pragma unroll
-        for (int v = 0; v < NV; v++) dd |= (pr.l[v] ^ sr.l[v]) | (pr.h[v] ^ sr.h[v]);
-        sr = next;
-      }
-      d |= live ? dd : 0u;
-    }
-    if (t != 0 && seg == segs - 1) {  // the tail chunk, bytes (wave 0: lanes 0-7 hold its symbols)
-      const uint8_t *ta = enc + s * enc_stride + whole, *tbp = rec + s * rec_stride + whole;
-      if (tid < 64) {
-        const uint32_t lane = tid < 8 ? tid : 0, h = t / 2;
-        Sym<1> s0;
-        ld_xor_tail(s0, ta, tbp, h, lane);
-        uint32_t dd = 0;
-        for (uint32_t r = r_lo; r < r_hi; r++) {
-          Sym<1> sr, pr;
-          ld_xor_tail(sr, ta + r * sb, tbp + r * sb, h, lane);
-          const Tab tab = dev::load_tab(tb + (r - 1));
-          dev::zero(pr);
-          dev::mul_add(pr, s0, tab);
-          dd |= (pr.l[0] ^ sr.l[0]) | (pr.h[0] ^ sr.h[0]);
-        }
-        d |= tid < 8 ? dd : 0u;
-      }
-    }
-    if (__builtin_amdgcn_ballot_w64(d != 0u) != 0ull && (tid & 63u) == 0u) reject[s] = 1;
+    const uint32_t at = dev::span_check<MODE, 1, false>(enc + s * enc_stride, rec + s * rec_stride, sb, rem % segs, segs,
+                                                        r_lo, r_hi, piv, nullptr,
+                                                        [&](int, uint32_t r) { return tb + (r - 1); });
+    if (__builtin_amdgcn_ballot_w64(at != dev::kNoSym) != 0ull && (threadIdx.x & 63u) == 0u) reject[s] = 1;
   }
 }
 
@@ -261,12 +203,6 @@ __global__ __launch_bounds__(256) void k_locate_finish(const int32_t *__restrict
     atomicAdd(counts + threadIdx.x, static_cast<unsigned long long>(part[threadIdx.x]));
 }
 
-// 2: 16-byte loads, 1: dwords, 0: bytes — what both buffers, both strides and sb allow
-int load_mode(const uint8_t *a, uint64_t a_stride, const uint8_t *b, uint64_t b_stride, uint64_t sb) {
-  const uint64_t al = reinterpret_cast<uint64_t>(a) | reinterpret_cast<uint64_t>(b) | a_stride | b_stride | sb;
-  return al % 16 == 0 ? 2 : al % 4 == 0 ? 1 : 0;
-}
-
 }  // namespace
 
 hipError_t launch_locate_classify(const uint8_t *enc, uint64_t enc_stride, const uint8_t *rec, uint64_t rec_stride,
@@ -276,19 +212,10 @@ hipError_t launch_locate_classify(const uint8_t *enc, uint64_t enc_stride, const
   if (n == 0) return hipSuccess;
   trace_launch("k_locate_classify");
   const dim3 grid(static_cast<uint32_t>(std::min<uint64_t>(n, 1u << 20)));
-  switch (load_mode(enc, enc_stride, rec, rec_stride, sb)) {
-    case 2:
-      hipLaunchKernelGGL(k_locate_classify<2>, grid, dim3(256), 0, s, enc, enc_stride, rec, rec_stride, sb, n, k, m,
-                         bad, rlog, dl, d_exp, d_log, tabs, cls);
-      break;
-    case 1:
-      hipLaunchKernelGGL(k_locate_classify<1>, grid, dim3(256), 0, s, enc, enc_stride, rec, rec_stride, sb, n, k, m,
-                         bad, rlog, dl, d_exp, d_log, tabs, cls);
-      break;
-    default:
-      hipLaunchKernelGGL(k_locate_classify<0>, grid, dim3(256), 0, s, enc, enc_stride, rec, rec_stride, sb, n, k, m,
-                         bad, rlog, dl, d_exp, d_log, tabs, cls);
-  }
+  with_int(load_mode(enc, enc_stride, rec, rec_stride, sb), kModes, [&](auto mode) {
+    hipLaunchKernelGGL(k_locate_classify<decltype(mode)::value>, grid, dim3(256), 0, s, enc, enc_stride, rec,
+                       rec_stride, sb, n, k, m, bad, rlog, dl, d_exp, d_log, tabs, cls);
+  });
   return hipGetLastError();
 }
 
@@ -297,22 +224,13 @@ hipError_t launch_locate_confirm(const uint8_t *enc, uint64_t enc_stride, const 
                                  const RsTab *tabs, uint8_t *reject, hipStream_t s) {
   if (n == 0 || m < 2) return hipSuccess;
   trace_launch("k_locate_confirm");
-  const uint64_t segs = (sb + kLocateSeg - 1) / kLocateSeg;
-  const uint32_t groups = (m - 1 + kLocateRows - 1) / kLocateRows;
+  const uint64_t segs = (sb + kSeg - 1) / kSeg;
+  const uint32_t groups = (m - 1 + kRows - 1) / kRows;
   const dim3 grid(static_cast<uint32_t>(std::min<uint64_t>(n * segs * groups, 1u << 20)));
-  switch (load_mode(enc, enc_stride, rec, rec_stride, sb)) {
-    case 2:
-      hipLaunchKernelGGL(k_locate_confirm<2>, grid, dim3(256), 0, s, enc, enc_stride, rec, rec_stride, sb, n, k, m,
-                         segs, groups, cls, tabs, reject);
-      break;
-    case 1:
-      hipLaunchKernelGGL(k_locate_confirm<1>, grid, dim3(256), 0, s, enc, enc_stride, rec, rec_stride, sb, n, k, m,
-                         segs, groups, cls, tabs, reject);
-      break;
-    default:
-      hipLaunchKernelGGL(k_locate_confirm<0>, grid, dim3(256), 0, s, enc, enc_stride, rec, rec_stride, sb, n, k, m,
-                         segs, groups, cls, tabs, reject);
-  }
+  with_int(load_mode(enc, enc_stride, rec, rec_stride, sb), kModes, [&](auto mode) {
+    hipLaunchKernelGGL(k_locate_confirm<decltype(mode)::value>, grid, dim3(256), 0, s, enc, enc_stride, rec,
+                       rec_stride, sb, n, k, m, segs, groups, cls, tabs, reject);
+  });
   return hipGetLastError();
 }
 

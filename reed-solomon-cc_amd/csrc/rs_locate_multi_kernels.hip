@@ -16,10 +16,11 @@
 // the last check found outside the span (kMlocNoPos: none).
 //  * k_mloc_check<MODE, NT>, round i = NT: flattened over (stripe, group of 16 rows, 16 KiB
 //    segment), grid-stride. Symbol p lies in the span iff S_r(p) == sum_j B_j[r] * S_{piv_j}(p) for
-//    every r: the NT pivot-row syndromes of a lane's unit stay in Sym<NV> registers while the
-//    group's rows pass. A lane that sees a difference contributes its symbol index; one atomicMin
-//    per wave. Round 0 (an empty basis) looks for a nonzero syndrome and reads only rows whose
-//    compare flag is set, so a clean stripe costs its flags.
+//    every r: dev::span_check (rs_device_span.hpp, the pass k_locate_confirm runs with one pivot)
+//    with the NT pivot rows piv[0, NT), rows from 0 and the position wanted. A lane that sees a
+//    difference contributes its symbol index; one atomicMin per wave. Round 0 (an empty basis)
+//    looks for a nonzero syndrome and reads only rows whose compare flag is set, so a clean stripe
+//    costs its flags.
 //  * k_mloc_extend, one workgroup per stripe: no failing symbol settles the stripe with rho = i;
 //    one at i == max_t makes it unlocated; otherwise S(pos) is reduced by the basis, normalised at
 //    its first nonzero row (the new pivot), the earlier vectors are reduced by it and all tables
@@ -33,22 +34,17 @@
 
 #include "rs_device.hpp"
 #include "rs_device_lanes.hpp"
+#include "rs_device_span.hpp"
 #include "rs_internal.hpp"
 
 namespace rs {
 namespace {
 
 using dev::build_tab;
-using dev::Lanes;
-using dev::ld_xor;
-using dev::ld_xor_tail;
-using dev::Sym;
-using dev::Tab;
-
-constexpr uint32_t kMlocSeg = 16384;             // as k_locate_confirm: a multiple of 16 and of 64
-constexpr uint32_t kMlocSegSyms = kMlocSeg / 2;  // symbols of a whole segment
-constexpr uint32_t kMlocRows = 16;               // rows of a work item
-constexpr uint32_t kNoSym = 0xFFFFFFFFu;
+using dev::kNoSym;
+using dev::kRows;
+using dev::kSeg;
+using dev::kSegSyms;
 
 // a * b for symbols a, b (log[0] is no logarithm: zero is tested)
 __device__ __forceinline__ uint32_t gf_mul_log(uint32_t a, uint32_t log_b, const uint16_t *__restrict__ d_exp,
@@ -71,113 +67,33 @@ __global__ __launch_bounds__(256) void k_mloc_check(const uint8_t *__restrict__ 
                                                     const uint8_t *__restrict__ bad,
                                                     const uint32_t *__restrict__ piv, const RsTab *__restrict__ tabs,
                                                     unsigned long long *pos) {
-  constexpr int NV = Lanes<MODE>::NV;
-  constexpr uint32_t kUnitsPerChunk = 8 / NV, kLo = 4 * NV;  // a unit: kLo low + kLo high bytes of one chunk
   const uint64_t per_stripe = segs * groups, total = n * per_stripe;
-  const uint32_t t = static_cast<uint32_t>(sb % 64);
-  const uint64_t whole = sb - t;
   const uint32_t tid = threadIdx.x;
   for (uint64_t w = blockIdx.x; w < total; w += gridDim.x) {
     const uint64_t s = w / per_stripe, rem = w % per_stripe;
     if (state[s] != kMlocActive) continue;  // settled: nothing to read
     const uint32_t g = static_cast<uint32_t>(rem / segs);
-    const uint64_t seg = rem % segs, base = seg * kMlocSeg;
+    const uint64_t seg = rem % segs;
     // an earlier segment already has a failing symbol (a stale value only costs time)
-    if (*static_cast<volatile unsigned long long *>(pos + s) < seg * kMlocSegSyms) continue;
-    const uint32_t r_lo = g * kMlocRows, r_hi = min(m, r_lo + kMlocRows);
+    if (*static_cast<volatile unsigned long long *>(pos + s) < seg * kSegSyms) continue;
+    const uint32_t r_lo = g * kRows, r_hi = min(m, r_lo + kRows);
     const uint8_t *flag = bad + s * m;
     if (NT == 0) {  // rows that agree hold no nonzero syndrome
       uint32_t any = 0;
       for (uint32_t r = r_lo; r < r_hi; r++) any |= flag[r];
       if (!any) continue;
     }
-    const uint8_t *pa = enc + s * enc_stride + base, *pb = rec + s * rec_stride + base;
     const RsTab *tb = tabs + s * max_t * m;
     uint32_t pr[NT > 0 ? NT : 1];
 #pragma unroll
     for (int j = 0; j < NT; j++) pr[j] = piv[s * max_t + j];
-    const uint32_t wb = base < whole ? static_cast<uint32_t>(whole - base < kMlocSeg ? whole - base : kMlocSeg) : 0;
-    const uint32_t units = wb / 64 * kUnitsPerChunk;
-    uint32_t at = kNoSym;  // the lane's smallest failing symbol, counted from the segment's first
-    // the loop bounds are workgroup-uniform (a lane past the end re-reads unit 0 and drops the
-    // result), so the table loads stay scalar
-    for (uint32_t u0 = 0; u0 < units; u0 += 256u) {
-      const bool live = u0 + tid < units;
-      const uint32_t u = live ? u0 + tid : 0;
-      const uint32_t off = u / kUnitsPerChunk * 64 + u % kUnitsPerChunk * kLo;
-      uint32_t dd[NV];
-#pragma unroll
-      for (int v = 0; v < NV; v++) dd[v] = 0;
-      if constexpr (NT == 0) {
-        for (uint32_t r = r_lo; r < r_hi; r++) {
-          if (!flag[r]) continue;
-          Sym<NV> sr;
-          ld_xor<MODE>(sr, pa + r * sb + off, pb + r * sb + off);
-#pragma unroll
-          for (int v = 0; v < NV; v++) dd[v] |= sr.l[v] | sr.h[v];
-        }
-      } else {
-        Sym<NV> sp[NT], sr;
-#pragma unroll
-        for (int j = 0; j < NT; j++) ld_xor<MODE>(sp[j], pa + pr[j] * sb + off, pb + pr[j] * sb + off);
-        ld_xor<MODE>(sr, pa + r_lo * sb + off, pb + r_lo * sb + off);
-        for (uint32_t r = r_lo; r < r_hi; r++) {
-          Sym<NV> next = sr, acc;
-          // the next row's loads are in flight while this row is multiplied
-          if (r + 1 < r_hi) ld_xor<MODE>(next, pa + (r + 1) * sb + off, pb + (r + 1) * sb + off);
-          dev::zero(acc);
-#pragma unroll
-          for (int j = 0; j < NT; j++) {
-            const Tab tab = dev::load_tab(tb + j * m + r);
-            dev::mul_add(acc, sp[j], tab);
-          }
-#pragma unroll
-          for (int v = 0; v < NV; v++) dd[v] |= (acc.l[v] ^ sr.l[v]) | (acc.h[v] ^ sr.h[v]);
-          sr = next;
-        }
-      }
-      if (live) {
-        const uint32_t first = u / kUnitsPerChunk * 32 + u % kUnitsPerChunk * kLo;  // the unit's first symbol
-#pragma unroll
-        for (int v = NV - 1; v >= 0; v--)
-          if (dd[v]) at = min(at, first + 4u * v + (static_cast<uint32_t>(__builtin_ctz(dd[v])) >> 3));
-      }
-    }
-    if (t != 0 && seg == segs - 1) {  // the tail chunk, bytes (wave 0: lanes 0-7 hold its symbols)
-      const uint8_t *ta = enc + s * enc_stride + whole, *tbp = rec + s * rec_stride + whole;
-      if (tid < 64) {
-        const uint32_t lane = tid < 8 ? tid : 0, h = t / 2;
-        uint32_t dd = 0;
-        if constexpr (NT == 0) {
-          for (uint32_t r = r_lo; r < r_hi; r++) {
-            Sym<1> sr;
-            ld_xor_tail(sr, ta + r * sb, tbp + r * sb, h, lane);
-            dd |= sr.l[0] | sr.h[0];
-          }
-        } else {
-          Sym<1> sp[NT];
-#pragma unroll
-          for (int j = 0; j < NT; j++) ld_xor_tail(sp[j], ta + pr[j] * sb, tbp + pr[j] * sb, h, lane);
-          for (uint32_t r = r_lo; r < r_hi; r++) {
-            Sym<1> sr, acc;
-            ld_xor_tail(sr, ta + r * sb, tbp + r * sb, h, lane);
-            dev::zero(acc);
-#pragma unroll
-            for (int j = 0; j < NT; j++) {
-              const Tab tab = dev::load_tab(tb + j * m + r);
-              dev::mul_add(acc, sp[j], tab);
-            }
-            dd |= (acc.l[0] ^ sr.l[0]) | (acc.h[0] ^ sr.h[0]);
-          }
-        }
-        // symbols past the tail's h read as zero on both sides: they never differ
-        if (tid < 8 && dd) at = min(at, wb / 2 + 4u * lane + (static_cast<uint32_t>(__builtin_ctz(dd)) >> 3));
-      }
-    }
+    // the lane's smallest failing symbol, counted from the segment's first
+    const uint32_t at = dev::span_check<MODE, NT, true>(enc + s * enc_stride, rec + s * rec_stride, sb, seg, segs, r_lo,
+                                                        r_hi, pr, flag, [&](int j, uint32_t r) { return tb + j * m + r; });
     if (__builtin_amdgcn_ballot_w64(at != kNoSym) != 0ull) {  // wave-uniform: one atomic per wave
       uint32_t lowest = at;
       for (int o = 32; o > 0; o >>= 1) lowest = min(lowest, static_cast<uint32_t>(__shfl_xor(static_cast<int>(lowest), o)));
-      if ((tid & 63u) == 0u) atomicMin(pos + s, static_cast<unsigned long long>(base / 2 + lowest));
+      if ((tid & 63u) == 0u) atomicMin(pos + s, static_cast<unsigned long long>(seg * kSegSyms + lowest));
     }
   }
 }
@@ -217,16 +133,8 @@ __global__ __launch_bounds__(256) void k_mloc_extend(const uint8_t *__restrict__
       if (tid == 0) state[s] = p == kMlocNoPos ? static_cast<int32_t>(round) : kLocUnlocated;
       continue;
     }
-    // the byte offsets of symbol p (k_locate_classify's addressing, the other way round)
-    const uint64_t t = sb % 64, whole = sb - t;
-    uint64_t lo, hi;
-    if (p < whole / 2) {
-      lo = p / 32 * 64 + p % 32;
-      hi = lo + 32;
-    } else {
-      lo = whole + (p - whole / 2);
-      hi = lo + t / 2;
-    }
+    uint64_t lo, hi;  // the byte offsets of symbol p
+    dev::symbol_bytes(sb, p, lo, hi);
     const uint8_t *pa = enc + s * enc_stride, *pb = rec + s * rec_stride;
     auto syndrome = [&](uint32_t r) {
       return static_cast<uint32_t>(pa[r * sb + lo] ^ pb[r * sb + lo]) |
@@ -379,36 +287,6 @@ __global__ __launch_bounds__(256) void k_mloc_finish(const int32_t *__restrict__
     atomicAdd(counts + threadIdx.x, static_cast<unsigned long long>(part[threadIdx.x]));
 }
 
-// 2: 16-byte loads, 1: dwords, 0: bytes — what both buffers, both strides and sb allow
-int load_mode(const uint8_t *a, uint64_t a_stride, const uint8_t *b, uint64_t b_stride, uint64_t sb) {
-  const uint64_t al = reinterpret_cast<uint64_t>(a) | reinterpret_cast<uint64_t>(b) | a_stride | b_stride | sb;
-  return al % 16 == 0 ? 2 : al % 4 == 0 ? 1 : 0;
-}
-
-template <int MODE>
-void launch_check_mode(uint32_t round, dim3 grid, hipStream_t s, const uint8_t *enc, uint64_t enc_stride,
-                       const uint8_t *rec, uint64_t rec_stride, uint64_t sb, uint64_t n, uint32_t m, uint32_t max_t,
-                       uint64_t segs, uint32_t groups, const int32_t *state, const uint8_t *bad, const uint32_t *piv,
-                       const RsTab *tabs, unsigned long long *pos) {
-#define RS_MLOC_CHECK(NT)                                                                                           \
-  case NT:                                                                                                          \
-    hipLaunchKernelGGL((k_mloc_check<MODE, NT>), grid, dim3(256), 0, s, enc, enc_stride, rec, rec_stride, sb, n, m, \
-                       max_t, segs, groups, state, bad, piv, tabs, pos);                                            \
-    break;
-  switch (round) {
-    RS_MLOC_CHECK(0)
-    RS_MLOC_CHECK(1)
-    RS_MLOC_CHECK(2)
-    RS_MLOC_CHECK(3)
-    RS_MLOC_CHECK(4)
-    RS_MLOC_CHECK(5)
-    RS_MLOC_CHECK(6)
-    RS_MLOC_CHECK(7)
-    RS_MLOC_CHECK(8)
-  }
-#undef RS_MLOC_CHECK
-}
-
 }  // namespace
 
 hipError_t launch_mloc_check(const uint8_t *enc, uint64_t enc_stride, const uint8_t *rec, uint64_t rec_stride,
@@ -417,26 +295,18 @@ hipError_t launch_mloc_check(const uint8_t *enc, uint64_t enc_stride, const uint
                              hipStream_t s) {
   if (n == 0) return hipSuccess;
   if (round > max_t || max_t > kMlocMaxT) return hipErrorInvalidValue;
-  const uint64_t segs = (sb + kMlocSeg - 1) / kMlocSeg;
-  const uint32_t groups = (m + kMlocRows - 1) / kMlocRows;
+  const uint64_t segs = (sb + kSeg - 1) / kSeg;
+  const uint32_t groups = (m + kRows - 1) / kRows;
   const dim3 grid(static_cast<uint32_t>(std::min<uint64_t>(n * segs * groups, 1u << 20)));
   unsigned long long *p = reinterpret_cast<unsigned long long *>(pos);
-  switch (load_mode(enc, enc_stride, rec, rec_stride, sb)) {
-    case 2:
-      trace_launch("k_mloc_check_x16");
-      launch_check_mode<2>(round, grid, s, enc, enc_stride, rec, rec_stride, sb, n, m, max_t, segs, groups, state, bad,
-                           piv, tabs, p);
-      break;
-    case 1:
-      trace_launch("k_mloc_check_x4");
-      launch_check_mode<1>(round, grid, s, enc, enc_stride, rec, rec_stride, sb, n, m, max_t, segs, groups, state, bad,
-                           piv, tabs, p);
-      break;
-    default:
-      trace_launch("k_mloc_check_x1");
-      launch_check_mode<0>(round, grid, s, enc, enc_stride, rec, rec_stride, sb, n, m, max_t, segs, groups, state, bad,
-                           piv, tabs, p);
-  }
+  static const char *const kNames[3] = {"k_mloc_check_x1", "k_mloc_check_x4", "k_mloc_check_x16"};
+  with_int(load_mode(enc, enc_stride, rec, rec_stride, sb), kModes, [&](auto mode) {
+    trace_launch(kNames[decltype(mode)::value]);
+    with_int(static_cast<int>(round), std::make_integer_sequence<int, kMlocMaxT + 1>(), [&](auto nt) {
+      hipLaunchKernelGGL((k_mloc_check<decltype(mode)::value, decltype(nt)::value>), grid, dim3(256), 0, s, enc,
+                         enc_stride, rec, rec_stride, sb, n, m, max_t, segs, groups, state, bad, piv, tabs, p);
+    });
+  });
   return hipGetLastError();
 }
 

@@ -32,6 +32,7 @@
 
 #include "rs_device.hpp"
 #include "rs_device_lanes.hpp"
+#include "rs_device_span.hpp"
 #include "rs_internal.hpp"
 
 namespace rs {
@@ -41,8 +42,7 @@ using dev::Lanes;
 using dev::Sym;
 using dev::Tab;
 
-constexpr uint32_t kUpdateSeg = 16384;  // as k_locate_confirm: a multiple of 16 and of 64
-constexpr uint32_t kUpdateRows = 16;
+constexpr uint32_t kUpdateSeg = dev::kSeg, kUpdateRows = dev::kRows;  // the scrub family's work item
 
 // ======================================================================= prepare
 // cl [k][m] = log c[r][j]. status may be nullptr.
@@ -236,30 +236,6 @@ __global__ __launch_bounds__(256) void k_update_apply(const uint8_t *__restrict_
   }
 }
 
-template <int MODE, int T>
-void launch_apply(const dim3 &grid, hipStream_t s, const uint8_t *d_old, const uint8_t *d_new, uint64_t change_stride,
-                  uint8_t *rec, uint64_t rec_stride, uint64_t sb, uint64_t n, uint32_t m, uint32_t max_u, uint64_t segs,
-                  uint32_t groups, const uint32_t *list, const uint32_t *live, const RsTab *tabs) {
-  hipLaunchKernelGGL((k_update_apply<MODE, T>), grid, dim3(256), 0, s, d_old, d_new, change_stride, rec, rec_stride, sb,
-                     n, m, max_u, segs, groups, list, live, tabs);
-}
-
-template <int MODE>
-void launch_apply_t(int tile, const dim3 &grid, hipStream_t s, const uint8_t *d_old, const uint8_t *d_new,
-                    uint64_t change_stride, uint8_t *rec, uint64_t rec_stride, uint64_t sb, uint64_t n, uint32_t m,
-                    uint32_t max_u, uint64_t segs, uint32_t groups, const uint32_t *list, const uint32_t *live,
-                    const RsTab *tabs) {
-  if (tile == 4)
-    launch_apply<MODE, 4>(grid, s, d_old, d_new, change_stride, rec, rec_stride, sb, n, m, max_u, segs, groups, list,
-                          live, tabs);
-  else if (tile == 2)
-    launch_apply<MODE, 2>(grid, s, d_old, d_new, change_stride, rec, rec_stride, sb, n, m, max_u, segs, groups, list,
-                          live, tabs);
-  else
-    launch_apply<MODE, 1>(grid, s, d_old, d_new, change_stride, rec, rec_stride, sb, n, m, max_u, segs, groups, list,
-                          live, tabs);
-}
-
 }  // namespace
 
 hipError_t launch_update_prepare(const uint32_t *index, uint64_t index_stride, uint32_t max_u, uint64_t n, uint32_t k,
@@ -277,10 +253,7 @@ hipError_t launch_update_apply(const uint8_t *d_old, const uint8_t *d_new, uint6
                                uint64_t rec_stride, uint64_t sb, uint64_t n, uint32_t m, uint32_t max_u,
                                const uint32_t *list, const uint32_t *live, const RsTab *tabs, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  // 2: 16-byte accesses, 1: dwords, 0: bytes — what every buffer, both strides and sb allow
-  const uint64_t al = reinterpret_cast<uint64_t>(d_old) | reinterpret_cast<uint64_t>(d_new) |
-                      reinterpret_cast<uint64_t>(rec) | change_stride | rec_stride | sb;
-  const int mode = al % 16 == 0 ? 2 : al % 4 == 0 ? 1 : 0;
+  const int mode = load_mode(d_old, d_new, rec, change_stride, rec_stride, sb);
   const int tile = max_u >= 3 ? 4 : static_cast<int>(max_u);
   static const char *const kNames[3][3] = {
       {"k_update_apply_x1_t1", "k_update_apply_x1_t2", "k_update_apply_x1_t4"},
@@ -290,15 +263,12 @@ hipError_t launch_update_apply(const uint8_t *d_old, const uint8_t *d_new, uint6
   const uint64_t segs = (sb + kUpdateSeg - 1) / kUpdateSeg;
   const uint32_t groups = (m + kUpdateRows - 1) / kUpdateRows;
   const dim3 grid(static_cast<uint32_t>(std::min<uint64_t>(n * segs * groups, 1u << 20)));
-  if (mode == 2)
-    launch_apply_t<2>(tile, grid, s, d_old, d_new, change_stride, rec, rec_stride, sb, n, m, max_u, segs, groups, list,
-                      live, tabs);
-  else if (mode == 1)
-    launch_apply_t<1>(tile, grid, s, d_old, d_new, change_stride, rec, rec_stride, sb, n, m, max_u, segs, groups, list,
-                      live, tabs);
-  else
-    launch_apply_t<0>(tile, grid, s, d_old, d_new, change_stride, rec, rec_stride, sb, n, m, max_u, segs, groups, list,
-                      live, tabs);
+  with_int(mode, kModes, [&](auto mc) {
+    with_int(tile, std::integer_sequence<int, 1, 2, 4>(), [&](auto tc) {
+      hipLaunchKernelGGL((k_update_apply<decltype(mc)::value, decltype(tc)::value>), grid, dim3(256), 0, s, d_old, d_new,
+                         change_stride, rec, rec_stride, sb, n, m, max_u, segs, groups, list, live, tabs);
+    });
+  });
   return hipGetLastError();
 }
 

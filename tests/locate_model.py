@@ -15,7 +15,7 @@ from rs_amd import reedsol_amd as R
 
 SB = 128  # two chunks: 64 symbols per shard
 CLEAN, RECOVERY_SET, UNLOCATED = R.LOCATE_CLEAN, R.LOCATE_RECOVERY_SET, R.LOCATE_UNLOCATED
-ROW_GROUP = 16  # the rows one work item of k_locate_confirm walks (kLocateRows)
+ROW_GROUP = 16  # the rows one work item of k_locate_confirm walks (dev::kRows)
 
 
 def encode(k, m, data):

@@ -30,16 +30,25 @@ class MultiCode(Code):
     def inv(self, a):
         return int(self.exp[(65535 - self.log[a]) % 65535])
 
+    def check_symbols(self, sb):
+        """the symbols the check reads (a mask over symbols()'s order): all of them"""
+        return np.ones(sb // 2, bool)
+
+    def check_rows(self):
+        """the rows the check compares with the span: all of them"""
+        return range(self.m)
+
     def span(self, S, max_t):
         """(basis [rho, m], pivot rows) of the span of the columns of S [m, P], or None when
         its rank exceeds max_t"""
         B = np.zeros((0, self.m), np.uint16)
         piv = []
+        read, rows = self.check_symbols(2 * S.shape[1]), list(self.check_rows())
         for rnd in range(max_t + 1):
             res = S.copy()  # S(p) reduced by the basis, every p at once
             for j, row in enumerate(piv):
                 res ^= self.mul(B[j][:, None], S[row][None, :])
-            failing = np.flatnonzero((res != 0).any(axis=0))
+            failing = np.flatnonzero((res[rows] != 0).any(axis=0) & read)
             if failing.size == 0:
                 return B, piv
             if rnd == max_t:

@@ -1,4 +1,5 @@
-"""Position sweeps for the detectors (rs_verify_batch_dev, rs_locate_batch_dev).
+"""Position sweeps for the detectors (rs_verify_batch_dev, rs_locate_batch_dev and
+rs_locate_multi_batch_dev at max_t = 1).
 A detector answers with a flag or a shard index per stripe, so a test observes only the byte
 positions it corrupts: a compare that never reads some bytes passes every test that leaves those
 bytes alone. This module corrupts them all, one stripe per probe. It is numpy and the oracle only
@@ -27,7 +28,9 @@ a region) and the GPU through the Python binding (tests/test_gpu_scrub_sweep.py)
 
 A verify back end is a callable (k, m, data [n, k, sb], stored [n, m, sb]) -> (flags [n, m],
 count, inputs_unchanged); a locate back end returns (located [n], present [n, k + m], counts [4],
-inputs_unchanged). The arrays handed over are read-only."""
+inputs_unchanged). The multi-shard entry point at max_t = 1 is a locate back end through
+multi_as_locate; check_locate is then told to consult that entry point's model (MultiCode) for
+the sweeps that need one. The arrays handed over are read-only."""
 import collections
 import functools
 
@@ -36,8 +39,9 @@ import numpy as np
 import oracle as O
 from helpers import splitmix_bytes
 from locate_model import CLEAN, RECOVERY_SET, UNLOCATED, Code, symbol_bytes, symbol_of
+from locate_multi_model import MultiCode
 
-SEG = 16384  # kVerifySeg == kLocateSeg == kUpdateSeg: the bytes of a shard one work item takes
+SEG = 16384  # the scrub family's segment (dev::kSeg, kVerifySeg): the bytes of a shard one work item takes
 PASSES = 4   # a segment is 4 passes of 256 lanes x 16 bytes (k_verify_compare<2>, k_locate_classify<2>)
 
 # a probed stripe. shard: the index in [0, k + m) of the shard that holds the probe's flip (highbyte:
@@ -325,6 +329,45 @@ def locate_reference(cls=Code):
     return run
 
 
+def multi_as_locate(backend):
+    """The multi-shard entry point at max_t = 1 as a locate back end. backend: (k, m, data, stored)
+    -> (count [n], located [n, 1], present [n, k + m], counts [3], inputs_unchanged). count 0 is
+    CLEAN, count 1 the located shard, unlocated stays UNLOCATED; counts [clean, one, unlocated]
+    become [clean, one, 0, unlocated]: the multi form has no RECOVERY_SET class."""
+    def run(k, m, data, stored):
+        count, located, present, counts, unchanged = backend(k, m, data, stored)
+        count, located = np.asarray(count), np.asarray(located)
+        assert located.shape == (count.shape[0], 1) and len(counts) == 3
+        assert np.isin(count, (0, 1, UNLOCATED)).all(), np.unique(count)
+        one = np.where(count == 1, located[:, 0], UNLOCATED)
+        loc = np.where(count == 0, CLEAN, one).astype(np.int32)
+        return loc, present, [counts[0], counts[1], 0, counts[2]], unchanged
+    return run
+
+
+def locate_multi_answers(code, S):
+    """the multi model's answer at max_t = 1 per stripe of the syndromes S [n, m, sb], in locate's
+    form -> (located, present)"""
+    n, m, _ = S.shape
+    located = np.full(n, CLEAN, np.int32)
+    present = np.ones((n, code.k + m), np.uint8)
+    for s in np.flatnonzero(S.any(axis=(1, 2))):
+        count, T = code.locate_multi_syndromes(S[s], 1)
+        if count == 1:
+            located[s], present[s, T[0]] = T[0], 0
+        elif count != 0:  # 0: a model that reads less than the whole stripe may see nothing
+            located[s] = UNLOCATED
+    return located, present
+
+
+def locate_multi_reference(cls=MultiCode):
+    """the locate back end of a multi model class (MultiCode, or a mutant of it) at max_t = 1"""
+    def run(k, m, data, stored):
+        located, present = locate_multi_answers(model(k, m, cls), O.encode_batch(k, m, data, threads=4) ^ stored)
+        return located, present, class_counts(located), True
+    return run
+
+
 # ------------------------------------------------------------------------ checker
 def _judge(sweep, rows_differ, what):
     """every stripe is judged: rows_differ [n] bool -> the failures, after the count of probed
@@ -354,12 +397,15 @@ def check_verify(sweep, backend):
     assert unchanged, f"{sweep.name} sweep: verify wrote an input"
 
 
-def check_locate(sweep, backend):
+def check_locate(sweep, backend, reference=Code):
     """Run a locate back end on the sweep: exactly the expected answers and present rows, the
     counts they imply, inputs unwritten. For the sweeps whose expectation rests on more than one
-    flipped bit (reject, highbyte) the reference back end must give it for every stripe first."""
+    flipped bit (reject, highbyte) the model of the back end under test must give it for every
+    stripe first: reference is that model's class, Code for locate, MultiCode for the multi-shard
+    locate at max_t = 1."""
     if sweep.name in ("reject", "highbyte"):
-        ref, _ = locate_answers(model(sweep.k, sweep.m), sweep.syndromes())
+        answers = locate_multi_answers if issubclass(reference, MultiCode) else locate_answers
+        ref, _ = answers(model(sweep.k, sweep.m, reference), sweep.syndromes())
         failures = _judge(sweep, ref != sweep.located, lambda s: f"the reference back end says {ref[s]}, the sweep "
                           f"expects {sweep.located[s]}: a degenerate probe")
         if failures:

@@ -70,8 +70,23 @@ class OnDevice:
         torch.cuda.synchronize()
         return located.cpu().numpy(), present.cpu().numpy(), counts.cpu().tolist(), self.unchanged()
 
+    def locate_multi(self, k, m, data, stored):
+        """rs_locate_multi_batch_dev at max_t = 1, for scrub_sweep.multi_as_locate"""
+        assert data is self.sweep.data and stored is self.sweep.stored
+        n = data.shape[0]
+        count = torch.full((n,), 77, dtype=torch.int32, device=DEV)
+        located = torch.full((n, 1), 55, dtype=torch.int32, device=DEV)
+        present = torch.full((n, k + m), 9, dtype=torch.uint8, device=DEV)
+        counts = torch.full((3,), -1, dtype=torch.int64, device=DEV)
+        R.locate_multi_batch_dev(k, m, self.d, self.p, 1, count=count, located=located, present=present, counts=counts)
+        self.kernels["locate_multi"] = ";".join(R.last_kernels())
+        torch.cuda.synchronize()
+        return count.cpu().numpy(), located.cpu().numpy(), present.cpu().numpy(), counts.cpu().tolist(), self.unchanged()
+
 
 def run(sweep, rec_offset=0, verify=True):
+    """verify (unless the sweep is locate's alone), locate and the multi-shard locate at max_t = 1
+    on one upload of the sweep"""
     dev = OnDevice(sweep, rec_offset)
     if verify:
         W.check_verify(sweep, dev.verify)
@@ -79,6 +94,11 @@ def run(sweep, rec_offset=0, verify=True):
     W.check_locate(sweep, dev.locate)
     for name in LOCATE_KERNELS:
         assert name in dev.kernels["locate"], dev.kernels
+    W.check_locate(sweep, W.multi_as_locate(dev.locate_multi), reference=W.MultiCode)
+    al = sweep.sb | rec_offset
+    check = "k_mloc_check_x16" if al % 16 == 0 else "k_mloc_check_x4" if al % 4 == 0 else "k_mloc_check_x1"
+    order = ["k_verify_compare"] + [check, "k_mloc_extend"] * 2 + ["k_mloc_match", "k_mloc_finish"]
+    assert dev.kernels["locate_multi"].endswith(";".join(order)), dev.kernels  # max_t + 1 rounds
     return dev
 
 

@@ -1,15 +1,16 @@
 """tests/scrub_sweep.py on the CPU: the generator's coverage conditions hold for every shard size
-the GPU file uses, the reference back ends pass every sweep, and nine back ends that each skip a
-region (what a kernel with a wrong loop bound, lane mask or row count would do) are caught, with
-every failing probe inside the region skipped. Small shards and a 256-byte segment keep the file
-at a few seconds; the geometry (segments, 4 passes, 16-byte slots, chunk halves, tail) is the
-kernels'."""
+the GPU file uses, the reference back ends (verify, locate and the multi-shard locate at max_t = 1)
+pass every sweep, and eleven back ends that each skip a region (what a kernel with a wrong loop
+bound, lane mask or row count would do) are caught, with every failing probe inside the region
+skipped. Small shards and a 256-byte segment keep the file at a few seconds; the geometry
+(segments, 4 passes, 16-byte slots, chunk halves, tail) is the kernels'."""
 import numpy as np
 import pytest
 
 import oracle as O
 import scrub_sweep as W
 from locate_model import UNLOCATED, Code
+from locate_multi_model import MultiCode
 
 SEG = 256
 K, M = 3, 2
@@ -70,6 +71,30 @@ def test_reference_passes_every_sweep(batch):
     for sweep in (W.reject_sweep(batch), W.highbyte_sweep(batch, originals=range(K))):
         assert sweep.nprobes == len(batch.probes)
         W.check_locate(sweep, W.locate_reference())
+
+
+def test_multi_reference_passes_every_sweep(batch):
+    """the multi-shard model at max_t = 1 gives locate's answers on every sweep (a reject stripe
+    has rank 2 > max_t), and its own guard excludes no stripe"""
+    for build in (W.recovery_sweep, W.original_sweep, W.reject_sweep):
+        sweep = build(batch)
+        W.check_locate(sweep, W.locate_multi_reference(), reference=MultiCode)
+    sweep = W.highbyte_sweep(batch, originals=range(K))
+    assert sweep.nprobes == len(batch.probes)
+    W.check_locate(sweep, W.locate_multi_reference(), reference=MultiCode)
+
+
+def test_multi_adapter():
+    """multi_as_locate: count 0 -> CLEAN, 1 -> located[0], unlocated -> UNLOCATED, the present
+    rows as returned, counts[3] -> [clean, one, 0, unlocated]"""
+    present = np.ones((3, K + M), np.uint8)
+    present[1, 4] = 0
+
+    def backend(k, m, data, stored):
+        return np.array([0, 1, UNLOCATED], np.int32), np.array([[-1], [4], [-1]], np.int32), present, [1, 1, 1], True
+
+    located, pres, counts, unchanged = W.multi_as_locate(backend)(K, M, None, None)
+    assert located.tolist() == [W.CLEAN, 4, UNLOCATED] and pres is present and counts == [1, 1, 0, 1] and unchanged
 
 
 def test_sweep_expectations(big):
@@ -243,6 +268,56 @@ def test_locate_mutant_first_row_group_only():
     assert {p.shard for _, _, p, _ in err.failures} == {k + 17} and len(err.failures) == len(coarse)
 
 
+# --------------------------------------------------------------------- multi mutants
+class NoTailCheck(MultiCode):
+    def check_symbols(self, sb):
+        return np.arange(sb // 2) < (sb - sb % 64) // 2
+
+
+class FirstGroupCheck(MultiCode):
+    def check_rows(self):
+        return range(min(self.m, 16))
+
+
+def failing_multi(sweep, cls):
+    with pytest.raises(W.ScrubSweepError) as e:
+        W.check_locate(sweep, W.locate_multi_reference(cls), reference=MultiCode)
+    return e.value
+
+
+def test_multi_mutant_no_tail_check(big):
+    """A check that never reads the tail symbols. Recovery and original sweeps: a stripe whose
+    probe lies in the tail looks clean. Reject sweep: a stripe is also wrong when its anchor lies
+    in the tail (every second one), because the mutant then sees the probe's shard alone."""
+    for build in (W.recovery_sweep, W.original_sweep):
+        sweep = build(big)
+        err = failing_multi(sweep, NoTailCheck)
+        assert err.offset >= 832 and "located -1" in str(err)
+        want = {s for s, p in enumerate(sweep.stripes) if p and p.offset >= 832}
+        assert len(want) >= 34 and {s for _, s, _, _ in err.failures} == want  # every tail byte is a probe
+    sweep = W.reject_sweep(big)
+    err = failing_multi(sweep, NoTailCheck)
+    want = {s for s, p in enumerate(sweep.stripes) if p and (p.offset >= 832 or p.anchor >= 832)}
+    assert {s for _, s, _, _ in err.failures} == want
+    assert any(p.anchor < 832 for _, _, p, _ in err.failures) and any(p.offset < 832 for _, _, p, _ in err.failures)
+
+
+def test_multi_mutant_first_row_group_only():
+    """m = 18: rows 0..15 are the check's first group, rows 16 and 17 its second"""
+    k, m, sb = 33, 18, 320
+    coarse = W.coarse_positions(sb, SEG)
+    rows = [r for r in range(1, m) for _ in coarse]
+    batch = W.Batch(k, m, sb, coarse * (m - 1), seg=SEG)
+    sweep = W.reject_sweep(batch, rows)
+    W.check_locate(sweep, W.locate_multi_reference(), reference=MultiCode)
+    err = failing_multi(sweep, FirstGroupCheck)
+    assert {p.shard for _, _, p, _ in err.failures} == {k + 16, k + 17} and len(err.failures) == 2 * len(coarse)
+    sweep = W.recovery_sweep(batch)  # shard s % m: a flip in row 16 or 17 alone looks clean
+    err = failing_multi(sweep, FirstGroupCheck)
+    want = {s for s, p in enumerate(sweep.stripes) if p and p.shard >= k + 16}
+    assert want and {s for _, s, _, _ in err.failures} == want
+
+
 def test_locate_mutant_high_byte_as_low(big):
     """Needs a code with coefficients outside GF(2^8). In RS(3, 2) every coefficient lies in the
     subfield the low bytes span, so a multiplication never mixes the bytes of a symbol: the
@@ -257,6 +332,7 @@ def test_locate_mutant_high_byte_as_low(big):
     batch = W.Batch(k, m, sb, W.positions(sb, SEG), seg=SEG)
     sweep = W.highbyte_sweep(batch)
     W.check_locate(sweep, W.locate_reference())
+    W.check_locate(sweep, W.locate_multi_reference(), reference=MultiCode)
     err = failing(sweep, HighAsLow)
     assert err.sweep == "highbyte"
     for _, s, p, _ in err.failures:  # every failing byte is a high byte: of a whole chunk or of the tail
